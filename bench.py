@@ -17,18 +17,20 @@ kept as the sub-object `config.sdpa_equal_lengths`.
 One "step" = ONE whole prune through the drop-in pruner API: capture of each tower's inputs by the model's own
 forward, block replay over the calibration samples, activation statistics, score / select / apply of every linear.
 Before each step the dense weights are copied back (7.4 GB device-to-device, ~3 ms, inside the timed region).
-`value` = 588 x steps / seconds.  `config.subtotals_s` (capture / replay / stat / select) come from ONE extra, untimed
+`value` = 588 x steps / seconds.  A plain run sets up, warms up, times the steps and prints the line; everything else
+is measured only with `--full`: `config.subtotals_s` (capture / replay / stat / select) come from ONE extra, untimed
 prune with synchronising phase timers.  `roofline` is measured inside the timed steps with HIP events carried by the
 kernel launches themselves (vlmc_set_launch_events -> hipExtLaunchKernel) on a rotating subset of the launches.
 `config.invariance`: the same prune once more as the reference's one-sample-per-forward loop on this GPU, and how many mask bits
 differ from the grouped replay's (0 expected).  `kernel_pass`: statistics + select kernels alone on resident activations.
+`--dump-outputs DIR` writes what the last timed prune handed its caller (see `dump_outputs`) as .npy files.
 
 N GPUs: `python bench.py --gpus N` starts N ranks by itself (torch.distributed.run as a child process, before this
 process touches a GPU); under a launcher (WORLD_SIZE set) it is one of the ranks.  The 128 calibration samples are
 sharded over the ranks (capture, replay and statistics scale 1/N), one RCCL all-gather of per-sample statistics per
 block, select replicated: total work fixed => "scaling": "strong".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 """
 import argparse
 import contextlib
@@ -60,6 +62,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed prune computed as DIR/<name>.npy (rank 0; a fixed, seeded sample of the weights)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: launch-event roofline inside the timed steps, phase "
+                         "sub-totals, invariance, per-rank floor, kernel pass, SDPA leg, CPU baseline (--cpu-seconds, --kernel-pass, "
+                         "--kernel-steps, --event-stride, --invariance, --sdpa-leg and --calib-local apply only with --full)")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the CPU-baseline leg (0 = skip)")
     ap.add_argument("--kernel-pass", default="auto", choices=["auto", "0", "1"],
                     help="also time the statistics + select kernels alone on resident activations (auto: only at N=1)")
@@ -80,7 +88,10 @@ def parse():
                          "every kernel a rank runs, the statistics exchange filled in with the rank's own rows "
                          "(VLMC_SIMULATE_WORLD, vlmc/shard.py); reported as config.per_rank_floor, never as the headline "
                          "(auto: all three at N=1, two prunes each)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -277,6 +288,9 @@ class PruneJob:
     def __init__(self, dev, reference_ops=False, ragged=False):
         from vlmc import synthetic
         self.dev = dev
+        # randomize_ redraws only the >= 2-D parameters; biases, norms and layer scales keep the constructor's init from the
+        # global generator -- seeded here, so that every run prunes the same model from the same data
+        torch.manual_seed(0)
         self.model = synthetic.InstructBlipT5(reference_ops=reference_ops).to(dev).eval()
         synthetic.randomize_(self.model, 0)
         # the parameters live in ONE buffer per dtype (views of it; 256-byte aligned), so that the weight restore that opens every timed
@@ -312,6 +326,9 @@ class PruneJob:
         with contextlib.redirect_stdout(io.StringIO()):
             pruner.prune()
 
+    def release(self):
+        self.model = self.flat = self.dense = self.batches = None
+
     def masks(self):
         return {n: m.mask.clone() for n, m in self.model.named_modules()
                 if isinstance(m, torch.nn.Linear) and isinstance(getattr(m, "mask", None), torch.Tensor)}
@@ -323,6 +340,31 @@ class PruneJob:
                 zeros += int((mod.weight == 0).sum())
                 total += mod.weight.numel()
         return zeros / max(1, total)
+
+    def dump_outputs(self, out_dir, per_linear=4096, seed=0):
+        """What the last prune handed its caller, for every pruned linear in module order (rows of each file): the mean
+        score (`weight.importance_score`), the number of kept weights and the sum of |pruned weight| over the whole tensor,
+        and the mask and pruned weight at `per_linear` positions drawn with a fixed seed (all of them would be 3.7 G
+        elements; 588 x 4096 x 2 x 4 B = 19 MB)."""
+        import numpy as np
+        os.makedirs(out_dir, exist_ok=True)
+        rng = np.random.default_rng(seed)
+        lins = [m for m in self.model.modules() if isinstance(m, torch.nn.Linear) and isinstance(getattr(m, "mask", None), torch.Tensor)]
+        w_s, m_s, sums = [], [], []
+        with torch.no_grad():
+            for mod in lins:
+                w = mod.weight
+                idx = torch.from_numpy(rng.integers(0, w.numel(), per_linear)).to(w.device)
+                w_s.append(w.reshape(-1)[idx].float())
+                m_s.append(mod.mask.reshape(-1)[idx].float())
+                sums.append(torch.stack([mod.mask.sum(dtype=torch.float64), w.abs().sum(dtype=torch.float64)]))
+            sums = torch.stack(sums).cpu().numpy()
+            arrays = {"weight_sample": torch.stack(w_s).cpu().numpy(), "mask_sample": torch.stack(m_s).cpu().numpy(),
+                      "kept_per_linear": sums[:, 0], "weight_abs_sum_per_linear": sums[:, 1],
+                      "importance_score_per_linear": np.array([float(getattr(m.weight, "importance_score", float("nan")))
+                                                               for m in lins], dtype=np.float64)}
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -661,23 +703,27 @@ def main():
         if padded is not None:
             groups.append(len(padded))
         return padded
-    cal.plan_groups, cal.plan_padded = counting, counting_padded
+    if args.full:
+        cal.plan_groups, cal.plan_padded = counting, counting_padded
 
     job = PruneJob(dev, reference_ops=True, ragged=True)
-    probe = LaunchProbe(args.event_stride)
-    install_probes(probe)
+    probe = LaunchProbe(args.event_stride) if args.full else None
+    if probe is not None:
+        install_probes(probe)
     for _ in range(args.warmup):
         job.step()
     sync()
     groups.clear()
-    probe.active = True
+    if probe is not None:
+        probe.active = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
         job.step()
     sync()
     elapsed = time.perf_counter() - t0
-    probe.active = False
-    probe.restore()
+    if probe is not None:
+        probe.active = False
+        probe.restore()
     cal.plan_groups, cal.plan_padded = real_plan, real_padded
     rank_ms = [elapsed / args.steps * 1e3]
     if world > 1:
@@ -686,6 +732,47 @@ def main():
         dist.all_reduce(every, op=dist.ReduceOp.SUM)
         rank_ms = [round(float(e) / args.steps * 1e3, 3) for e in every.tolist()]
         elapsed = max(every.tolist())
+    if args.dump_outputs and rank == 0:                 # before any other prune of --full overwrites the model
+        job.dump_outputs(args.dump_outputs)
+
+    sec = elapsed / args.steps
+    n_lin = 588
+    out = {
+        "metric": "layers/sec + total prune wall-clock, InstructBLIP-FlanT5-XL Wanda@50% (588 linears, 128 calib samples)",
+        "value": round(n_lin * args.steps / elapsed, 1), "unit": "layers/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(sec * 1e3, 3), "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f16/bf16", "data": "synthetic",
+        "config": {"workload": "configs[1]: one whole load_pruner('blipt5_wanda_pruner').prune() -- Wanda 50% unstructured, "
+                               "InstructBLIP-FlanT5-XL architecture and shapes (39 ViT-g blocks fp16 matrix-wide rule + 24/24 "
+                               "Flan-T5-XL blocks bf16 per-row rule; between them the 12-layer Q-Former, never pruned), the blocks written "
+                               "with the REFERENCE'S OP SEQUENCE (eva_vit.py:129-168: q / v bias, explicit q @ k^T, softmax, attn @ v; "
+                               "modeling_t5.py:520-640: torch.matmul scores, bucketed position bias of block 0, extended masks, fp32 "
+                               "softmax; Qformer.py:205-246), random init, 128 batch-1 calibration samples with RAGGED text (257 image "
+                               "tokens, 32 queries + prompts of 8..128 tokens, answers of 4..16 tokens)",
+                   "linears": n_lin, "blocks": 87, "calib_samples": N_CALIB, "ratio": RATIO,
+                   "total_prune_wall_clock_s": round(sec, 4), "blocks_per_s": round(87 / sec, 1),
+                   "replay": f"grouped: up to {os.environ.get('VLMC_BATCH_REPLAY', '128')} samples per block forward; ragged samples "
+                             "padded into one group, the linears skip the padding rows (vlmc_linear_fwd_rows)",
+                   "timed_with_launch_events": args.full,
+                   "parallelism": f"calib-dp{world}", "backend": backend,
+                   "world_size": dist.get_world_size() if world > 1 else 1,
+                   "per_rank_ms_per_step": rank_ms,
+                   "exchange": ("one all-gather of the per-sample statistics rows per block (87 per prune); seconds inside them in the "
+                                "phase-timed prune (--full): subtotals_s.exchange (includes the ranks' arrival skew)") if world > 1 else None},
+    }
+    if args.full:
+        full_legs(args, job, probe, groups, world, elapsed, out)
+    job = None
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        print(json.dumps(out))
+
+
+def full_legs(args, job, probe, groups, world, elapsed, out):
+    """--full: what the bench measures and checks besides the headline, added to `out` (the result line)."""
+    dev = job.dev
     pruned_fraction = job.pruned_fraction()
     per_tower = {}
     if groups and args.steps:
@@ -785,7 +872,7 @@ def main():
             finally:
                 os.environ.pop("VLMC_SIMULATE_WORLD", None)
 
-    job = None
+    job.release()                                 # (the model's 15 GB, before the kernel pass and the SDPA leg's own model)
     torch.cuda.empty_cache()
     kp = None
     if args.kernel_pass == "1" or (args.kernel_pass == "auto" and world == 1):
@@ -806,44 +893,12 @@ def main():
         except Exception as e:
             sdpa = {"error": f"{type(e).__name__}: {e}"}
 
-    out = None
-    if rank == 0:
-        sec = elapsed / args.steps
-        n_lin = 588
-        out = {
-            "metric": "layers/sec + total prune wall-clock, InstructBLIP-FlanT5-XL Wanda@50% (588 linears, 128 calib samples)",
-            "value": round(n_lin * args.steps / elapsed, 1), "unit": "layers/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(sec * 1e3, 3), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f16/bf16", "data": "synthetic",
-            "config": {"workload": "configs[1]: one whole load_pruner('blipt5_wanda_pruner').prune() -- Wanda 50% unstructured, "
-                                   "InstructBLIP-FlanT5-XL architecture and shapes (39 ViT-g blocks fp16 matrix-wide rule + 24/24 "
-                                   "Flan-T5-XL blocks bf16 per-row rule; between them the 12-layer Q-Former, never pruned), the blocks written "
-                                   "with the REFERENCE'S OP SEQUENCE (eva_vit.py:129-168: q / v bias, explicit q @ k^T, softmax, attn @ v; "
-                                   "modeling_t5.py:520-640: torch.matmul scores, bucketed position bias of block 0, extended masks, fp32 "
-                                   "softmax; Qformer.py:205-246), random init, 128 batch-1 calibration samples with RAGGED text (257 image "
-                                   "tokens, 32 queries + prompts of 8..128 tokens, answers of 4..16 tokens)",
-                       "linears": n_lin, "blocks": 87, "calib_samples": N_CALIB, "ratio": RATIO,
-                       "total_prune_wall_clock_s": round(sec, 4), "blocks_per_s": round(87 / sec, 1),
-                       "pruned_fraction": round(pruned_fraction, 6), "subtotals_s": sub,
-                       "replay": f"grouped: up to {os.environ.get('VLMC_BATCH_REPLAY', '128')} samples per block forward; ragged samples "
-                                 "padded into one group, the linears skip the padding rows (vlmc_linear_fwd_rows)",
-                       "groups_per_block_forward": per_tower,
-                       "capture": capture_info(), "invariance": invariance,
-                       "parallelism": f"calib-dp{world}", "backend": backend, "per_rank_floor": floor,
-                       "sdpa_equal_lengths": sdpa,
-                       "world_size": dist.get_world_size() if world > 1 else 1,
-                       "per_rank_ms_per_step": rank_ms,
-                       "exchange": ("one all-gather of the per-sample statistics rows per block (87 per prune); seconds inside them in the "
-                                    "phase-timed prune: subtotals_s.exchange (includes the ranks' arrival skew)") if world > 1 else None},
-            "roofline": roofline,
-            "kernel_pass": kp,
-        }
-        out["cpu_baseline"] = cpu_baseline(args.cpu_seconds) if world == 1 and args.cpu_seconds > 0 else None
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(out))
+    out["config"].update({"pruned_fraction": round(pruned_fraction, 6), "subtotals_s": sub, "groups_per_block_forward": per_tower,
+                          "capture": capture_info(), "invariance": invariance, "per_rank_floor": floor,
+                          "sdpa_equal_lengths": sdpa})
+    out["roofline"] = roofline
+    out["kernel_pass"] = kp
+    out["cpu_baseline"] = cpu_baseline(args.cpu_seconds) if world == 1 and args.cpu_seconds > 0 else None
 
 
 if __name__ == "__main__":

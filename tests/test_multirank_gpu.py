@@ -37,7 +37,7 @@ def _run(cmd, env=None, timeout=900):
 @pytest.mark.timeout(1200)
 @pytest.mark.parametrize("world", [2, 4])          # (8 ranks on one device would exceed the box's limit of 6 GPU processes:
 def test_bench_launches_its_own_ranks_and_shards_the_prune(world):      # tests/test_dist_world48.py covers 8 over gloo on the CPU)
-    r = _run([sys.executable, "bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--cpu-seconds", "0", "--kernel-pass", "0"],
+    r = _run([sys.executable, "bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--full", "--cpu-seconds", "0", "--kernel-pass", "0"],
              env={"VLMC_BENCH_ONE_DEVICE": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
