@@ -68,10 +68,7 @@ extern "C" int vlmc_attn_fwd_lens(const void *Q, const void *K, const void *V, v
     a.nblk = int((Tq + 15) / 16);
     a.bpw = 6;
     {
-        static const bool dma_ok = [] {
-            const char *e = getenv("VLMC_ATTN_DMA");                          // 0: K and V staged through registers (the cross-check)
-            return !(e && e[0] == '0');
-        }();
+        static const bool dma_ok = env_flag("VLMC_ATTN_DMA", true);          // 0: K and V staged through registers (the cross-check)
         const uintptr_t bits = reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V) |
                                uintptr_t(2 * (a.sk_b | a.sk_h | a.sk_t | a.sv_b | a.sv_h | a.sv_t));
         a.dma = dma_ok && (bits & 15u) == 0;

@@ -305,8 +305,8 @@ extern "C" int vlmc_attn_matmul(const void *A, const void *B, void *C, int dtype
     VLMC_REQUIRE(grid < (int64_t(1) << 31), "vlmc_attn_matmul: too many tiles");
     // B with K == 1 or N == 1 satisfies both layouts: take the one whose stride says so (sb_k == 1 first: no transposition)
     const bool nn = sb_k != 1;
-    const char *e = getenv("VLMC_ATTN_TR");                        // 0: transpose the NN operand while writing LDS (the cross-check;
-    const bool tr = !(e && e[0] == '0');                           // read per call so that a test can hold both against each other)
+    const bool tr = env_flag("VLMC_ATTN_TR", true);                // 0: transpose the NN operand while writing LDS (the cross-check;
+                                                                   // read per call so that a test can hold both against each other)
     hipStream_t s = as_stream(stream);
     const dim3 g{unsigned(grid)}, b{unsigned(NT_)};
     if (dtype == VLMC_BF16) {

@@ -9,6 +9,8 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 
 #include "../../include/vlmc.h"
 
@@ -151,6 +153,26 @@ LaunchEvents take_launch_events();                 // returns the pending pair (
         if (ev_.start || ev_.stop) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, ev_.start, ev_.stop, 0, __VA_ARGS__); \
         else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                              \
     } while (0)
+
+// ---- VLMC_* environment switches: the library's only getenv (every name is registered in vlmc/config.py, with the
+// default the call site passes).  One rule, as on the Python side: a flag is on unless its value is "0".
+inline const char *env_text(const char *name) { return getenv(name); }
+inline bool env_flag(const char *name, bool dflt) {
+    const char *e = env_text(name);
+    return e ? strcmp(e, "0") != 0 : dflt;
+}
+inline int env_int(const char *name, int dflt) {
+    const char *e = env_text(name);
+    return e ? atoi(e) : dflt;
+}
+
+// CUs of the current device, or `fallback` when the runtime cannot tell
+inline int device_cu_count(int fallback) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+        return fallback;
+    return n;
+}
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -507,8 +507,7 @@ static int simulate_dispatch(const void *W, int64_t out_f, int64_t in_f, int64_t
     // 6144x1408 linear vs 1.5 / 2.0 / 4.9 ms with 2 / 4 / 8 waves), rows of 4096 columns with four (2.2 ms vs 3.2 ms
     // with two and 4.0 ms with eight).
     int nw = nchunks <= 256 ? 1 : (nchunks <= 768 ? 4 : 8);
-    if (const char *e = getenv("VLMC_DSNOT_NW")) {                    // tuning override
-        const int f = atoi(e);
+    if (const int f = env_int("VLMC_DSNOT_NW", 0)) {                  // tuning override
         if ((f == 1 || f == 2 || f == 4 || f == 8) && nchunks <= int64_t(64) * f * 4) nw = f;
     }
     if (nchunks > int64_t(64) * nw * 4) {
@@ -597,8 +596,7 @@ extern "C" int vlmc_dsnot_refine(const void *W, int dtype, int64_t out_features,
         VLMC_REQUIRE(prune_m == 2 || prune_m == 4 || prune_m == 8, "vlmc_dsnot_refine: n:m needs m in {2,4,8} (got %d)", prune_m);
     hipStream_t st = as_stream(stream);
     // fast path: sorted-list heads + O(1) cycles (dsnot_lists.hip); VLMC_DSNOT_LISTS=0 keeps the per-cycle reductions
-    const char *use_lists = getenv("VLMC_DSNOT_LISTS");
-    if (!(use_lists && atoi(use_lists) == 0)) {
+    if (env_flag("VLMC_DSNOT_LISTS", true)) {
         const int rc = dsnot_refine_lists(W, dtype, out_features, in_features, ldw, keep_mask0, sqrt_scaler, sum_row, var_row,
                                           use_wanda_init, prune_n, prune_m, max_cycle, update_threshold, pow_of_var,
                                           without_same_sign, events, stop_cycle, st);

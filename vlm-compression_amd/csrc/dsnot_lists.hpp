@@ -843,14 +843,12 @@ static int lists_dispatch(const void *W, int64_t out_f, int64_t in_f, int64_t ld
     while (nw < 8 && nchunks > int64_t(64) * nw * 4) nw *= 2;
     if (nw == 1 && nchunks > 128) nw = 2;   // 129..256 chunks: two waves with 2 chunks per lane (one wave with 4: 174 VGPRs, 2 waves per SIMD; 6144 x 1408: 339 -> 277 us)
     if (NM && nw == 1) nw = 2;      // n:m: 23 KB of LDS per row -> six one-wave workgroups per CU would leave the SIMDs at 1.5 waves
-    if (const char *e = getenv("VLMC_DSNOT_NW")) {
-        const int f = atoi(e);
+    if (const int f = env_int("VLMC_DSNOT_NW", 0)) {
         if ((f == 1 || f == 2 || f == 4 || f == 8) && nchunks <= int64_t(64) * f * 4 && !(NM && f == 1)) nw = f;
     }
     if (nchunks > int64_t(64) * nw * 4) return VLMC_EINVAL;
     const int ch = nchunks <= int64_t(64) * nw * 2 ? 2 : 4;
-    const char *radix_only = getenv("VLMC_DSNOT_RADIX_ONLY");      // the exact route alone (tests compare the two)
-    const int fast = (radix_only && atoi(radix_only)) ? 0 : 1;
+    const int fast = env_flag("VLMC_DSNOT_RADIX_ONLY", false) ? 0 : 1;   // the exact route alone (tests compare the two)
 #define VLMC_DL(CH, NW)                                                                                                    \
     hipLaunchKernelGGL((dsnot_lists_kernel<T, CH, NW, NM>), dim3(unsigned(out_f)), dim3(64 * NW), 0, st,                    \
                        static_cast<const raw *>(W), out_f, in_f, ldw, keep0, sq, sum_row, var_row, use_wanda_init, prune_m, \

@@ -211,16 +211,9 @@ int launch_f32(const char *what, const F32Gemm &g, int64_t batches, hipStream_t 
         set_error("%s: more than 65535 matrices in a batch", what);
         return VLMC_EINVAL;
     }
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
+    static const int cus = device_cu_count(256);
     auto tiles = [&](int t) { return int64_t((g.N + t - 1) / t) * ((g.M + t - 1) / t) * batches; };
-    static const int forced = [] {
-        const char *e = getenv("VLMC_F32_TILE");                       // A/B: 128 / 64 / 32 for every fp32 launch (same bits)
-        return e ? atoi(e) : 0;
-    }();
+    static const int forced = env_int("VLMC_F32_TILE", 0);             // A/B: 128 / 64 / 32 for every fp32 launch (same bits)
     if (forced == 128) return launch_f32_tw<4>(what, g, batches, s);
     if (forced == 64) return launch_f32_tw<2>(what, g, batches, s);
     if (forced == 32) return launch_f32_tw<1>(what, g, batches, s);

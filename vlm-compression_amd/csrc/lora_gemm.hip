@@ -695,23 +695,13 @@ void fill_common(LoraArgs &a, const void *W, int64_t ldw, const uint8_t *mask, c
     a.sparse = sparse != 0;
     a.hs = dtype == VLMC_F16 ? half_bits_if_exact(scaling) : 0;
     a.fast = dtype == VLMC_F16 && a.hs != 0;
-    {
-        const char *e = getenv("VLMC_LORA_DBG");
-        a.dbg = e ? atoi(e) : 0;
-    }
+    a.dbg = env_int("VLMC_LORA_DBG", 0);
 }
 
 // rows of activations per tile: the choice (256 or 192) that leaves the fewer rounds of workgroups on the chip, then the less padding
 int pick_bq(int64_t M, int nbp) {
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
-    static const int forced = [] {
-        const char *e = getenv("VLMC_LORA_BQ");
-        return e ? atoi(e) : 0;
-    }();
+    static const int cus = device_cu_count(256);
+    static const int forced = env_int("VLMC_LORA_BQ", 0);
     if (forced == 192 || forced == 256) return forced;
     auto cost = [&](int bq) {
         const int64_t tiles = int64_t(nbp) * ((M + bq - 1) / bq), rounds = (tiles + cus - 1) / cus;

@@ -54,10 +54,7 @@ extern "C" int vlmc_sdpa_fwd(const void *Q, const void *K, const void *V, void *
     }
     a.scale_log2e = scale * 1.44269504088896340736f;
     {
-        static const bool dma_ok = [] {
-            const char *e = getenv("VLMC_SDPA_DMA");                          // 0: K and V staged through registers (the cross-check)
-            return !(e && e[0] == '0');
-        }();
+        static const bool dma_ok = env_flag("VLMC_SDPA_DMA", true);          // 0: K and V staged through registers (the cross-check)
         const uintptr_t bits = reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V) | uintptr_t(2 * (sk_b | sk_h | sk_t | sv_b | sv_h | sv_t));
         a.dma = dma_ok && (bits & 15u) == 0;
     }

@@ -417,11 +417,7 @@ __global__ void lora_grad_reduce2_kernel(const float *__restrict__ part_a, int s
 // first version aimed at ">= 768 = 3 per CU": 512 ran, the other 256 made a second, half-empty round -- 4096 x 4096: 68 -> 54 us,
 // 11008 x 4096: 134 -> 101 us with one full round.)
 static int64_t grad_row_splits(int64_t out_f, int64_t in_f) {
-    static const int64_t resident = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return int64_t(2) * n;
-    }();
+    static const int64_t resident = int64_t(2) * device_cu_count(256);
     const int64_t strips = (in_f + kTN - 1) / kTN, tiles = (out_f + kTM - 1) / kTM;
     int64_t s = resident / strips;                   // the most splits that still fit one round
     if (s > tiles) s = tiles;

@@ -621,11 +621,7 @@ extern "C" int vlmc_sparsegpt_select_sweep(float *W, int64_t count, int64_t ldw,
     int dev = 0;
     static int cus[64] = {0};
     if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (dev < 64 && cus[dev] == 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 64;
-        cus[dev] = v;
-    }
+    if (dev < 64 && cus[dev] == 0) cus[dev] = device_cu_count(64);
     const int64_t max_wgs = 2 * int64_t(dev < 64 ? cus[dev] : 64);
     int rows = 0;
     for (int r : {1, 2, 4, 8}) {
@@ -662,8 +658,7 @@ extern "C" int vlmc_sparsegpt_select_sweep(float *W, int64_t count, int64_t ldw,
         }
         once.mark(d2);
     }
-    int force_fail = 0;
-    if (const char *e = getenv("VLMC_SGPT_SELECT_FORCE_FAIL")) force_fail = atoi(e);       // tests: 1..3 = fail at that level
+    const int force_fail = env_int("VLMC_SGPT_SELECT_FORCE_FAIL", 0);                      // tests: 1..3 = fail at that level
 #define VLMC_SELSWEEP(R)                                                                                                      \
     hipLaunchKernelGGL((sgpt_select_sweep_kernel<R>), dim3(unsigned(sc.wg0[n_scopes])), dim3(256), lds, as_stream(stream), W,   \
                        int(count), ldw, U1, ldu, sc, Err1, lde, mask_out, ldmo, static_cast<uint32_t *>(workspace), force_fail)

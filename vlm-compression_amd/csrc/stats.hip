@@ -190,8 +190,7 @@ static int pick_vec(const vlmc_stat_job &j, size_t esz, int64_t n_calls) {
         if (n_calls * (j.in_features / v) >= want_threads) { vec = v; chosen = true; }
     }
     if (!chosen && narrowest) vec = narrowest;
-    if (const char *e = getenv("VLMC_SQNORM_VEC")) {   // tuning override (must be legal)
-        const int v = atoi(e);
+    if (const int v = env_int("VLMC_SQNORM_VEC", 0)) {   // tuning override (must be legal)
         if ((v == 1 || v == 2 || v == 4 || (v == 8 && esz == 2)) && (v == 1 || ok(v))) vec = v;
     }
     return vec;

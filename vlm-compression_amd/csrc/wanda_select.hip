@@ -1575,10 +1575,9 @@ static int64_t n_partials(int mode, int64_t out_f) {
     return mode == VLMC_SEL_ROW ? out_f : (mode == VLMC_SEL_MATRIX ? kMatrixParts : kNmParts);
 }
 
-static int env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
+constexpr uint32_t kSelectSampleMargin = 9;        // rank margin of the row selects' sample (~ +-3 sigma of a 32-sample rank)
+constexpr int64_t kSelectWantWaves = 4096;         // waves a row-select launch aims for (~4 per SIMD)
+constexpr int kMatrixWgs = 512;                    // workgroups of the multi-launch matrix-wide select (2 x 1024 lanes per CU)
 
 static bool job_aligned(const vlmc_select_job &j) {
     return j.in_features % 8 == 0 && j.ldw % 8 == 0 && aligned16(j.W) && aligned16(j.sqrt_scaler) &&
@@ -1604,7 +1603,7 @@ static int launch_rows(const vlmc_select_job *jobs, const int *idx, int n, int a
     }
     SelBatch b;
     b.n = n; b.apply_zero = apply_zero;
-    b.p0 = uint32_t(env_int("VLMC_SELECT_SAMPLE_MARGIN", 9));          // ~ +-3 sigma of a 32-sample rank
+    b.p0 = kSelectSampleMargin;
     b.p1 = 0;
     int64_t rows = 0;
     for (int i = 0; i < n; ++i) {
@@ -1623,11 +1622,7 @@ static int launch_rows(const vlmc_select_job *jobs, const int *idx, int n, int a
     }
     int nw = 1;
     while (nw < 8 && nchunks > int64_t(64) * nw * 4) nw *= 2;               // CH <= 4
-    const int64_t want_waves = env_int("VLMC_SELECT_WANT_WAVES", 4096);      // ~4 waves per SIMD
-    while (nw < 8 && rows * nw < want_waves && nchunks > int64_t(64) * nw) nw *= 2;
-    if (const int f = env_int("VLMC_SELECT_NW", 0)) {
-        if ((f == 1 || f == 2 || f == 4 || f == 8) && nchunks <= int64_t(64) * f * 4) nw = f;
-    }
+    while (nw < 8 && rows * nw < kSelectWantWaves && nchunks > int64_t(64) * nw) nw *= 2;
     const int ch = int((nchunks + 64 * nw - 1) / (64 * nw));
 #define VLMC_ROWS_NW(NW)                          \
     switch (ch) {                                 \
@@ -1650,7 +1645,7 @@ static int launch_rows(const vlmc_select_job *jobs, const int *idx, int n, int a
 // All SEL_ROW jobs of a call in one mixed launch: possible when every job is 16-byte aligned, every row fits
 // 4 waves x 4 chunks (in <= 8192) and both widths occur (one width alone: launch_rows is the tuned path).
 static bool mixed_rows_eligible(const vlmc_select_job *jobs, int n_jobs) {
-    if (n_jobs < 2 || n_jobs > kMaxSelJobs || !env_int("VLMC_SELECT_MIXED", 1)) return false;
+    if (n_jobs < 2 || n_jobs > kMaxSelJobs || !env_flag("VLMC_SELECT_MIXED", true)) return false;
     bool narrow = false, wide = false;
     for (int i = 0; i < n_jobs; ++i) {
         if (!job_aligned(jobs[i]) || jobs[i].in_features > 8192) return false;
@@ -1663,17 +1658,16 @@ template <typename T>
 static int launch_rows_mixed(const vlmc_select_job *jobs, int n_jobs, int apply_zero, hipStream_t st) {
     SelBatch b;
     b.n = n_jobs; b.apply_zero = apply_zero;
-    b.p0 = uint32_t(env_int("VLMC_SELECT_SAMPLE_MARGIN", 9));
+    b.p0 = kSelectSampleMargin;
     b.p1 = 0;
     uint32_t units = 0;
     int64_t max_chunks = 0;
     int n = 0;
-    const bool wide_first = env_int("VLMC_MIXED_WIDE_FIRST", 1) != 0;   // (0: narrow first -- measured 62.5 vs 58.9 us per T5 block)
-    for (int pass = 0; pass < 2; ++pass) {                      // wide jobs first
+    for (int pass = 0; pass < 2; ++pass) {                      // wide jobs first (narrow first: measured 62.5 vs 58.9 us per T5 block)
         for (int i = 0; i < n_jobs; ++i) {
             const vlmc_select_job &j = jobs[i];
             const bool is_wide = j.in_features > 2048;
-            if (is_wide != (pass == (wide_first ? 0 : 1))) continue;
+            if (is_wide != (pass == 0)) continue;
             fill_job(b.job[n], j);
             units += uint32_t(is_wide ? j.out_features : (j.out_features + 3) / 4);
             b.job[n].unit_end = units;
@@ -1702,12 +1696,12 @@ template <typename T>
 static int launch_matrix(const vlmc_select_job *jobs, const int *idx, int n, int apply_zero, hipStream_t st) {
     SelBatch b;
     b.n = n; b.apply_zero = apply_zero;
-    b.p0 = uint32_t(env_int("VLMC_MATRIX_FORCE_SLOW", 0)); b.p1 = 0;
+    b.p0 = uint32_t(env_int("VLMC_MATRIX_FORCE_SLOW", 0)); b.p1 = 0;      // tests: force the slow route at that barrier
     bool aligned = true;
     uint32_t wgs = 0;
     // persistent workgroups: 2 x 1024 lanes per CU over the whole launch, shared out by matrix size, so the
     // fixed per-workgroup latencies (control loads, LDS clear/flush, done-counter atomic) are paid once
-    const int budget = env_int("VLMC_MATRIX_WGS", 512);
+    const int budget = kMatrixWgs;
     int64_t all_chunks = 0;
     for (int i = 0; i < n; ++i) all_chunks += jobs[idx[i]].out_features * ((jobs[idx[i]].in_features + 7) / 8);
     for (int i = 0; i < n; ++i) {
@@ -1722,15 +1716,15 @@ static int launch_matrix(const vlmc_select_job *jobs, const int *idx, int n, int
     }
     int64_t max_in = 0;
     for (int i = 0; i < n; ++i) max_in = jobs[idx[i]].in_features > max_in ? jobs[idx[i]].in_features : max_in;
-    if (env_int("VLMC_MATRIX_FUSED", 1) && max_in <= kFusedMaxIn) {
+    if (env_flag("VLMC_MATRIX_FUSED", true) && max_in <= kFusedMaxIn) {
         // one workgroup per CU at most: co-resident by construction (see matrix_fused_kernel)
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            cus < n) {
+        const int cus = device_cu_count(0);
+        if (cus < n) {
             set_error("vlmc_wanda_select: cannot query the device's CU count");
             return VLMC_EHIP;
         }
-        int fbudget = env_int("VLMC_MATRIX_FUSED_WGS", cus) < cus ? env_int("VLMC_MATRIX_FUSED_WGS", cus) : cus;
+        const int fwgs = env_int("VLMC_MATRIX_FUSED_WGS", cus);         // tests: fewer workgroups
+        int fbudget = fwgs < cus ? fwgs : cus;
         if (fbudget > kMaxFusedWgs) fbudget = kMaxFusedWgs;
         if (fbudget < n) fbudget = n;
         uint32_t total = 0;

@@ -23,13 +23,12 @@ every world size.  `VLMC_SHARD_CALIB=0` restores the reference's replica behavio
 from __future__ import annotations
 
 import contextlib
-import os
 import threading
 
 import torch
 import torch.nn as nn
 
-from vlmc import forward, phases
+from vlmc import config, forward, phases
 
 # The engine's parts (round 6: this file was 2 700 lines): what they share, the grouping / padding of samples, finished towers, the capture
 # phases.  Their names are re-exported here -- the pruners, bench.py and the tests import this module.
@@ -115,7 +114,7 @@ class _TailStop(ValueError):
 def tail_skip_enabled():
     """`VLMC_SKIP_DEAD_TAIL=0`: run the statistics pass to the end of the block like the reference (:308-311 writes
     `outs[j]` in that pass too, and overwrites every one of them in the second pass before anything reads them)."""
-    return os.environ.get("VLMC_SKIP_DEAD_TAIL", "1") != "0"
+    return config.flag("VLMC_SKIP_DEAD_TAIL")
 
 
 class statistics_only:

@@ -4,13 +4,12 @@ into one forward and checked against a sample's own forward bit for bit (`_captu
 from __future__ import annotations
 
 import contextlib
-import os
 import threading
 
 import torch
 import torch.nn as nn
 
-from vlmc import forward, phases
+from vlmc import config, forward, phases
 
 from lavis.compression.pruners import replay_towers as towers_
 from lavis.compression.pruners.replay_state import (  # noqa: F401
@@ -91,7 +90,7 @@ def _capture_block_inputs(model, dataloader, n_samples, module_to_process, forwa
                 # if the trouble is not the merge (out of memory, a broken model) the per-sample route meets it again and raises
                 # Out of memory is not a refusal of the stacked batch, and `VLMC_STRICT=1` (CI of the engine itself) wants every such
                 # exception raised: a regression inside the merged path must not hide behind its fallback.
-                if isinstance(e, torch.cuda.OutOfMemoryError) or os.environ.get("VLMC_STRICT") == "1":
+                if isinstance(e, torch.cuda.OutOfMemoryError) or config.flag("VLMC_STRICT"):
                     raise
                 res = None
                 graph_stats["merged_capture_errors"] = graph_stats.get("merged_capture_errors", 0) + 1
@@ -139,7 +138,7 @@ def _capture_block_inputs(model, dataloader, n_samples, module_to_process, forwa
 
 
 try:
-    MERGED_CAPTURE_MIN = max(2, int(os.environ.get("VLMC_CAPTURE_MERGED_MIN", "24")))
+    MERGED_CAPTURE_MIN = max(2, config.integer("VLMC_CAPTURE_MERGED_MIN"))
 except ValueError:
     MERGED_CAPTURE_MIN = 24
 
@@ -147,7 +146,7 @@ except ValueError:
 def merged_capture_enabled():
     """Calibration batches of one structure run the model's forward to the next tower as ONE stacked batch
     (`_capture_merged`; `VLMC_CAPTURE_MERGED=0`: one forward per calibration batch, as the reference's loop)."""
-    return os.environ.get("VLMC_CAPTURE_MERGED", "1") != "0" and tower_batch_enabled() and replay_group_size() > 1 and \
+    return config.flag("VLMC_CAPTURE_MERGED") and tower_batch_enabled() and replay_group_size() > 1 and \
         graph_replay_enabled() and torch.cuda.is_available()
 
 
@@ -290,14 +289,14 @@ def _capture_merged(model, batches, module_to_process, forward_to_cache, lora_mo
         # forward is postponed at a finished tower's first block, the tower runs ONCE, padded, for the samples of all groups
         # (TowerGraph.enter_group -> run_deferred -> _run_padded) and the groups' forwards are repeated.
         defer = len(order) > 2
-        if defer and not (os.environ.get("VLMC_CAPTURE_MERGED_RAGGED", "1") == "1" and tower_pad_enabled() and tower_graph_enabled()):
+        if defer and not (config.flag("VLMC_CAPTURE_MERGED_RAGGED") and tower_pad_enabled() and tower_graph_enabled()):
             # (on since round 6: the encoder's phase of the ragged reference-op prune is 55-59 ms instead of 100 in the synchronising
             # phase timers.  In round 5 the whole prune was level with it -- the per-sample Python it removes ran behind the GPU tail of
             # the preceding walk -- but with the linears skipping the padding rows that tail is shorter and the host shows: 479 -> 463 ms,
             # same box, tools/ragged_prof.py)
             return None
         pruned_on_the_way = [t for t in towers if not t.memo_serves and t.path not in towers_.FROZEN_TOWERS]
-        if defer and pruned_on_the_way and (os.environ.get("VLMC_CAPTURE_MERGED_PRUNED", "1") == "0" or
+        if defer and pruned_on_the_way and (not config.flag("VLMC_CAPTURE_MERGED_PRUNED") or
                                             not all(t.predicted for t in pruned_on_the_way)):
             # ragged batches and a PRUNED tower on the way whose outputs are not remembered (the decoder's phase: 24 encoder blocks).
             # Round 5 measured 145-173 ms for that phase on this route against 87 per sample: every group's forward ran twice (postponed

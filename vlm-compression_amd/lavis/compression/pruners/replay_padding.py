@@ -4,7 +4,6 @@ of finished towers (`replay_towers.TowerGraph`).  Split out of `calibration.py` 
 from __future__ import annotations
 
 import contextlib
-import os
 import threading
 
 import torch
@@ -18,6 +17,7 @@ from lavis.compression.pruners.replay_state import (  # noqa: F401
     _bits_equal,
     pad_ragged_enabled,
     replay_group_size,
+    replay_token_budget,
 )
 
 
@@ -26,10 +26,7 @@ def plan_groups(cur_in, caches, n_samples, group_max):
     shapes and dtypes (they need not be neighbours: real calibration text is ragged), at most `group_max` per call and at
     most `VLMC_REPLAY_TOKENS` (default 65536) rows of activations per call.  Returns lists of sample indices, ordered by
     their first member; the statistics keep the reference's per-sample order whatever the grouping."""
-    try:
-        budget = max(1, int(os.environ.get("VLMC_REPLAY_TOKENS", str(REPLAY_TOKEN_BUDGET))))
-    except ValueError:
-        budget = REPLAY_TOKEN_BUDGET
+    budget = replay_token_budget()
     buckets = {}
     for j in range(n_samples):
         buckets.setdefault(_stack_key(cur_in[j], caches[j]), []).append(j)
@@ -119,10 +116,7 @@ def plan_padded(cur_in, caches, n_samples, group_max):
         return None                                                   # nothing to hide padded keys behind
     if ragged_s and (None in S or not isinstance(c0.get("encoder_attention_mask"), torch.Tensor)):
         return None
-    try:
-        budget = max(1, int(os.environ.get("VLMC_REPLAY_TOKENS", str(REPLAY_TOKEN_BUDGET))))
-    except ValueError:
-        budget = REPLAY_TOKEN_BUDGET
+    budget = replay_token_budget()
     # Which samples share a padded forward: ONE group.  (Buckets of similar length -- up to three, 26-34 % fewer rows -- were measured
     # slower in round 5, 486 / 541 against 478 ms: a T5 block forward is ~45 launches whatever its rows; since round 6 the linears skip
     # the padding rows and the fused attention the padding keys, so the rows buckets would save are hardly computed any more.  Removed.)

@@ -6,13 +6,12 @@ public names), `replay_capture.py` (the capture phases), `replay_towers.py` (fin
 from __future__ import annotations
 
 import contextlib
-import os
 import threading
 
 import torch
 import torch.nn as nn
 
-from vlmc import forward, phases
+from vlmc import config, forward, phases
 
 from vlmc.shard import calibration_shard  # noqa: E402,F401  (one answer for capture, replay and the exchanges)
 
@@ -58,7 +57,7 @@ def release_tower_memory():
     The calibration activations are ordinary tensors whose memory returns to the caching allocator when they go out of
     scope; handing it back to the driver and sweeping the Python heap cost ~0.1 s per prune of FlanT5-XL for nothing the next
     tower needs, so both are opt-in: `VLMC_RELEASE_MEMORY=1`."""
-    if os.environ.get("VLMC_RELEASE_MEMORY", "0") == "1":
+    if config.flag("VLMC_RELEASE_MEMORY"):
         import gc
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
@@ -77,7 +76,7 @@ def _keys_for(model_prefix):
 
 def graph_replay_enabled():
     """Graph-captured replay (default on for GPU tensors, `VLMC_GRAPH_REPLAY=0` turns it off)."""
-    return os.environ.get("VLMC_GRAPH_REPLAY", "1") != "0"
+    return config.flag("VLMC_GRAPH_REPLAY")
 
 
 GRAPH_MIN_SAMPLES = 4         # a capture costs about three eager forwards
@@ -125,7 +124,7 @@ def _bits_equal(r, v):
 
 def tower_memo_enabled():
     """Outputs of a finished tower are remembered from one capture phase to the next (`VLMC_TOWER_MEMO=0`: off)."""
-    return os.environ.get("VLMC_TOWER_MEMO", "1") != "0"
+    return config.flag("VLMC_TOWER_MEMO")
 
 
 def capture_graph(fn, device):
@@ -164,7 +163,7 @@ def capture_streams():
     160 us where streaming its 96 MB of weights takes 19); independent samples on S streams fill it.  Same kernels, same
     arguments, same results."""
     try:
-        return max(1, int(os.environ.get("VLMC_CAPTURE_STREAMS", "4")))
+        return max(1, config.integer("VLMC_CAPTURE_STREAMS"))
     except ValueError:
         return 1
 
@@ -186,7 +185,7 @@ def quiet_gc(fn):
     @functools.wraps(fn)
     def wrapper(*args, **kwargs):
         global _gc_depth
-        mine = _gc_depth == 0 and os.environ.get("VLMC_GC_FREEZE", "1") != "0" and gc.isenabled() and gc.get_freeze_count() == 0
+        mine = _gc_depth == 0 and config.flag("VLMC_GC_FREEZE") and gc.isenabled() and gc.get_freeze_count() == 0
         if mine:
             gc.freeze()
         _gc_depth += 1
@@ -201,35 +200,35 @@ def quiet_gc(fn):
 
 def tower_batch_enabled():
     """Finished towers run for all calibration samples of one shape in ONE pass (`VLMC_TOWER_BATCH=0`: per sample)."""
-    return os.environ.get("VLMC_TOWER_BATCH", "1") != "0"
+    return config.flag("VLMC_TOWER_BATCH")
 
 
 def tower_predict_enabled():
     """A finished tower's stacked pass starts from the block-0 arguments remembered from its own capture phase
     (TowerGraph.run_predicted; `VLMC_TOWER_PREDICT=0`: every forward is aborted at block 0 and repeated, as in round 3)."""
-    return os.environ.get("VLMC_TOWER_PREDICT", "1") != "0"
+    return config.flag("VLMC_TOWER_PREDICT")
 
 
 def tower_pad_enabled():
     """Ragged samples of one argument structure run a finished tower as ONE padded stacked pass (TowerGraph._run_padded;
     `VLMC_TOWER_PAD=0`: one pass per token count, as before)."""
-    return os.environ.get("VLMC_TOWER_PAD", "1") != "0" and pad_ragged_enabled()
+    return config.flag("VLMC_TOWER_PAD") and pad_ragged_enabled()
 
 
 def tower_graph_enabled():
     """One HIP graph per finished TOWER and calibration forward (`VLMC_TOWER_GRAPH=0`: one per block)."""
-    return os.environ.get("VLMC_TOWER_GRAPH", "1") != "0"
+    return config.flag("VLMC_TOWER_GRAPH")
 
 
 def later_check_enabled():
     """`VLMC_LATER_EQUAL=0`: every comparison of a remembered input with the one at hand waits for its answer."""
-    return os.environ.get("VLMC_LATER_EQUAL", "1") != "0"
+    return config.flag("VLMC_LATER_EQUAL")
 
 
-REPLAY_GROUP_DEFAULT = 128
+REPLAY_GROUP_DEFAULT = int(config.DEFAULTS["VLMC_BATCH_REPLAY"])
 
 
-REPLAY_TOKEN_BUDGET = 1 << 16
+REPLAY_TOKEN_BUDGET = int(config.DEFAULTS["VLMC_REPLAY_TOKENS"])
 
 
 def replay_group_size():
@@ -237,14 +236,22 @@ def replay_group_size():
     (default 128, i.e. the whole calibration set of the reference's scripts; `VLMC_BATCH_REPLAY=1` is the reference's
     per-sample loop, replayed from HIP graphs)."""
     try:
-        return max(1, int(os.environ.get("VLMC_BATCH_REPLAY", str(REPLAY_GROUP_DEFAULT))))
+        return max(1, config.integer("VLMC_BATCH_REPLAY"))
     except ValueError:
         return REPLAY_GROUP_DEFAULT
 
 
+def replay_token_budget():
+    """`VLMC_REPLAY_TOKENS=R`: at most R rows of activations per block forward (default 65536)."""
+    try:
+        return max(1, config.integer("VLMC_REPLAY_TOKENS"))
+    except ValueError:
+        return REPLAY_TOKEN_BUDGET
+
+
 def pad_ragged_enabled():
     from vlmc import forward as fw
-    return os.environ.get("VLMC_PAD_RAGGED", "1") != "0" and fw.enabled() and fw.attn_matmul_enabled() and fw.softmax_enabled()
+    return config.flag("VLMC_PAD_RAGGED") and fw.enabled() and fw.attn_matmul_enabled() and fw.softmax_enabled()
 
 
 def block_tensors(layer):

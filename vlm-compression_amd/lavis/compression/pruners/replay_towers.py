@@ -4,13 +4,12 @@ between (`FROZEN_TOWERS`), and the deferred bit-for-bit comparisons of a phase (
 from __future__ import annotations
 
 import contextlib
-import os
 import threading
 
 import torch
 import torch.nn as nn
 
-from vlmc import forward, phases
+from vlmc import config, forward, phases
 
 from lavis.compression.pruners.replay_state import (  # noqa: F401
     MEMO_MAX_BYTES,
@@ -182,7 +181,7 @@ class TowerMemo:
         not a copy -- the copies were 1 700 launches and 190 MB of traffic per prune for the Q-Former's arguments alone (every sample's
         image states), and the walk's inputs / a seeded tower's outputs have always been kept this way.  `VLMC_MEMO_COPY=1`: copies."""
         d = v.detach()
-        if os.environ.get("VLMC_MEMO_COPY", "0") == "1":
+        if config.flag("VLMC_MEMO_COPY"):
             return d.clone()
         d._vlmc_version = d._version                      # (the alias shares the version counter of what it was detached from)
         return d
@@ -420,7 +419,7 @@ class TowerGraph:
     # (9 ms for the 24 T5 encoder blocks: two of them were 18 of the 26 ms a rank of 8 spends capturing the decoder's inputs).
     # `VLMC_TOWER_TRACES=2`: rounds 2-4's two identical traces.
     try:
-        NEED = max(1, int(os.environ.get("VLMC_TOWER_TRACES", "1")))
+        NEED = max(1, config.integer("VLMC_TOWER_TRACES"))
     except ValueError:
         NEED = 1
 
@@ -500,7 +499,7 @@ class TowerGraph:
         if key is None:
             return False
         w = self.wirings.get(key)
-        if w is None and os.environ.get("VLMC_TOWER_SHARE_WIRING", "1") != "0":
+        if w is None and config.flag("VLMC_TOWER_SHARE_WIRING"):
             k2 = self.by_struct.get(self._struct(key))
             if k2 is not None and self.wirings.get(k2):
                 w = self.wirings[key] = self.wirings[k2]
@@ -527,7 +526,7 @@ class TowerGraph:
             self.live = self.trace = self.btrace = None
             key = self._key0(args, kwargs)
             wiring = self._wiring(key)
-            if os.environ.get("VLMC_DEBUG_TOWERS"):
+            if config.flag("VLMC_DEBUG_TOWERS"):
                 print("TOWER", getattr(self, "path", "?"), "sample", _CTX.capture_sample, "key", key is not None, "wiring",
                       None if wiring is None else (False if wiring is False else "known"), "ready", len(self.ready), "predicted", len(self.predicted),
                       "batchable", self._batchable(args, kwargs) if key is not None else None, "memo_serves", self.memo_serves, flush=True)
@@ -614,7 +613,7 @@ class TowerGraph:
                 # the last block's outputs, which the model does compute on, are stacked into tensors of their own as before
                 ps, t0 = recs[0].get("pass"), recs[0].get("t")
                 near = ps is not None and all(r.get("pass") is ps and r.get("t") == t0 + k_ for k_, r in enumerate(recs)) and \
-                    len({ps["lens"][r["t"]] for r in recs}) == 1 and os.environ.get("VLMC_GROUP_VIEWS", "1") != "0"
+                    len({ps["lens"][r["t"]] for r in recs}) == 1 and config.flag("VLMC_GROUP_VIEWS")
                 n_views = self.n - 1 if near else 0
                 whole = len(ps["lens"]) if near else 0
                 for i in range(n_views):
@@ -678,7 +677,7 @@ class TowerGraph:
     def _begin_batched_trace(self, key, args, kwargs, ext):
         j = _CTX.capture_sample
         if self.NEED != 1 or j is None or not (tower_batch_enabled() and tower_predict_enabled()) or self.memo_serves or \
-                os.environ.get("VLMC_TOWER_BATCHED_TRACE", "1") == "0" or j not in self.predicted or not self._batchable(args, kwargs):
+                not config.flag("VLMC_TOWER_BATCHED_TRACE") or j not in self.predicted or not self._batchable(args, kwargs):
             return None
         group = []
         for jj in sorted(self.predicted):
@@ -956,7 +955,7 @@ class TowerGraph:
         if not self.predicted or self.memo_serves or self.off or not (tower_batch_enabled() and tower_predict_enabled()):
             return set()
         out, count = set(), {}
-        shared = os.environ.get("VLMC_TOWER_SHARE_WIRING", "1") != "0" and tower_pad_enabled()
+        shared = config.flag("VLMC_TOWER_SHARE_WIRING") and tower_pad_enabled()
         for j in samples:
             rec = self.predicted.get(j)
             if rec is None:

@@ -11,7 +11,6 @@ is attached (SparseGPT only rewrites the weights).  The arithmetic lives in `vlm
 """
 from __future__ import annotations
 
-import os
 
 import torch
 
@@ -19,6 +18,7 @@ from lavis.common.registry import registry
 from lavis.compression.pruners import calibration as cal
 from lavis.compression.pruners.layer_single_base_pruner import LayerWiseBasePruner
 from lavis.compression.pruners.utils import print_time
+from vlmc import config
 from lavis.compression.pruners.wanda_pruner import uniform_or_layer_sparsity
 
 _KW = dict(prune_spec=None, importance_scores_cache=None, keep_indices_or_masks_cache=None, is_strct_pruning=False,
@@ -146,7 +146,7 @@ def _shard_linears(subset, wrapped):
     rows * n per sweep).  Returns {linear name: rank}, or None when running single / as replicas
     (`VLMC_SGPT_SHARD_LAYERS=0`: every rank prunes everything)."""
     rank, world = cal.calibration_shard()
-    if world == 1 or os.environ.get("VLMC_SGPT_SHARD_LAYERS", "1") == "0":
+    if world == 1 or not config.flag("VLMC_SGPT_SHARD_LAYERS"):
         return None
     groups = {}
     for name in subset:

@@ -22,7 +22,6 @@ There is no CPU fallback: without the HIP library or a GPU model the pruner rais
 """
 from __future__ import annotations
 
-import os
 
 import torch
 
@@ -30,9 +29,9 @@ from lavis.common.registry import registry
 from lavis.compression.pruners import calibration as cal
 from lavis.compression.pruners.layer_single_base_pruner import LayerSparsity, LayerWiseBasePruner
 from lavis.compression.pruners.utils import print_time
-from vlmc import phases
+from vlmc import config, phases
 
-_VERBOSE = os.environ.get("VLMC_VERBOSE", "0") != "0"
+_VERBOSE = config.flag("VLMC_VERBOSE")
 
 
 # --------------------------------------------------------------------------------------

@@ -5,8 +5,10 @@ import ctypes
 import os
 import re
 
+from . import config
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("VLMC_LIB", os.path.join(_HERE, "libvlmc_hip.so"))   # VLMC_LIB: tuning builds
+LIB_PATH = config.text("VLMC_LIB") or os.path.join(_HERE, "libvlmc_hip.so")   # VLMC_LIB: tuning builds
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "vlmc.h")
 
 VLMC_OK, VLMC_EINVAL, VLMC_EHIP, VLMC_EWORKSPACE, VLMC_ENOTPD = 0, -1, -2, -3, -4

@@ -23,7 +23,6 @@ module as before, only `forward` is replaced."""
 from __future__ import annotations
 
 import contextlib
-import os
 import threading
 import weakref
 
@@ -31,7 +30,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import config, ops
 
 _active = 0
 stats = {"kernel": 0, "library": 0, "grouped_launches": 0, "served_from_group": 0, "stash_dropped": 0, "attn_kernel": 0,
@@ -44,17 +43,17 @@ _SIBLINGS = weakref.WeakKeyDictionary()
 
 
 def enabled():
-    return os.environ.get("VLMC_LINEAR_FWD", "1") != "0"
+    return config.flag("VLMC_LINEAR_FWD")
 
 
 def grouping_enabled():
-    return os.environ.get("VLMC_LINEAR_GROUP", "1") != "0"
+    return config.flag("VLMC_LINEAR_GROUP")
 
 
 def f32_enabled():
     """fp32 linears / attention products / GELU of a replayed forward on the batch-invariant fp32 kernels (the reference's fp32
     Q-Former); `VLMC_LINEAR_F32=0`: fp32 modules stay with the library, as before round 6 (a finished fp32 tower is then not stacked)."""
-    return os.environ.get("VLMC_LINEAR_F32", "1") != "0"
+    return config.flag("VLMC_LINEAR_F32")
 
 
 def _prepare(x, weight, bias):
@@ -85,7 +84,7 @@ _ROW_MAPS = None
 
 
 def row_map_enabled():
-    return os.environ.get("VLMC_ROW_MAP", "1") != "0"
+    return config.flag("VLMC_ROW_MAP")
 
 
 _PAD_LENGTHS = None           # {padded tokens: int32 device tensor [samples]}: each sample's own token rows (the fused attention skips the rest)
@@ -121,7 +120,7 @@ def padded_rows(maps, lengths=None, host=None):
     on = row_map_enabled()
     _ROW_MAPS = maps if (maps and on) else None
     _PAD_LENGTHS = lengths if (lengths and on) else None
-    _PAD_HOST = host if (host and on and os.environ.get("VLMC_ROW_SLICES", "1") != "0") else None
+    _PAD_HOST = host if (host and on and config.flag("VLMC_ROW_SLICES")) else None
     _SLICES = {}
     try:
         yield
@@ -379,13 +378,13 @@ class _Tracker:
 # the original.  A second thread that enters `invariant_matmuls` while another one holds the patches
 # runs unpatched (its products go to the library: the replay of ONE prune is what the kernels are promised for).
 _mm_depth = 0
-_mm_saved = {}
+_mm_saved = []               # (owner, attribute, original or None: inherited, `del` restores) of the installed patches
 _mm_owner = None
 _ident = threading.get_ident
 
 
 def attn_matmul_enabled():
-    return os.environ.get("VLMC_ATTN_MATMUL", "1") != "0"
+    return config.flag("VLMC_ATTN_MATMUL")
 
 
 # ---- the reference-op attention chain in ONE launch ---------------------------------------------------------------------------
@@ -412,7 +411,7 @@ _LAZY_LIVE = weakref.WeakSet()    # lazy tensors somebody still holds: realized 
 
 
 def attn_fused_enabled():
-    return os.environ.get("VLMC_ATTN_FUSED", "1") != "0"
+    return config.flag("VLMC_ATTN_FUSED")
 
 
 _LAZY_META_PROPS = {"shape", "dtype", "device", "ndim", "is_cuda", "requires_grad", "layout", "is_sparse", "is_quantized", "is_meta",
@@ -795,7 +794,7 @@ def _make_softmax(orig, functional):
 
 
 def softmax_enabled():
-    return os.environ.get("VLMC_SOFTMAX", "1") != "0"
+    return config.flag("VLMC_SOFTMAX")
 
 
 def _make_gelu(orig):
@@ -821,7 +820,7 @@ def _make_gelu(orig):
 
 
 def function_mode_enabled():
-    return os.environ.get("VLMC_TORCH_FUNCTION_MODE", "0") == "1"
+    return config.flag("VLMC_TORCH_FUNCTION_MODE")
 
 
 class _ReplayMode(torch.overrides.TorchFunctionMode):
@@ -830,7 +829,7 @@ class _ReplayMode(torch.overrides.TorchFunctionMode):
 
     def __init__(self, table):
         super().__init__()
-        self.table = table
+        self.table = {orig: handler for _owner, _name, orig, handler in table}
 
     def __torch_function__(self, func, types, args=(), kwargs=None):
         h = self.table.get(func)
@@ -840,23 +839,22 @@ class _ReplayMode(torch.overrides.TorchFunctionMode):
 
 
 def _function_table():
-    """function object -> handler, for the switches in force (built per context: the closures read the switches when made)"""
-    import torch.nn.functional as F_
+    """The replay's routing for the switches in force: a list of (owner, attribute, original, handler) -- the attribute patches set
+    `owner.attribute = handler`, the function mode sends a call of `original` to `handler`.  Built per context: the closures read
+    the switches when made.  `torch.Tensor`'s methods are inherited from TensorBase: the original is the base's."""
     base = torch._C.TensorBase
-    t = {}
-    for f in (torch.matmul, torch.bmm, base.__matmul__, base.matmul, base.bmm):
-        t[f] = _make_matmul(f)
-    if os.environ.get("VLMC_SDPA", "1") != "0":
-        t[F_.scaled_dot_product_attention] = _make_sdpa(F_.scaled_dot_product_attention)
-    if softmax_enabled():
-        t[F_.softmax] = _make_softmax(F_.softmax, True)
-        t[torch.softmax] = _make_softmax(torch.softmax, False)
-        t[base.softmax] = _make_softmax(base.softmax, False)
-    if os.environ.get("VLMC_GELU", "1") != "0":
-        t[F_.gelu] = _make_gelu(F_.gelu)
-    if os.environ.get("VLMC_ROW_MEAN", "1") != "0":
-        t[torch.mean] = _make_mean(torch.mean)
-        t[base.mean] = _make_mean(base.mean)
+    t = [(owner, name, f, _make_matmul(f)) for owner, name, f in [
+        (torch, "matmul", torch.matmul), (torch, "bmm", torch.bmm),
+        (torch.Tensor, "__matmul__", base.__matmul__), (torch.Tensor, "matmul", base.matmul), (torch.Tensor, "bmm", base.bmm)]]
+    if config.flag("VLMC_SDPA"):                 # fused attention written as F.scaled_dot_product_attention
+        t.append((F, "scaled_dot_product_attention", F.scaled_dot_product_attention, _make_sdpa(F.scaled_dot_product_attention)))
+    if softmax_enabled():                        # the attention's fp32 softmax: padding-invariant
+        t += [(F, "softmax", F.softmax, _make_softmax(F.softmax, True)), (torch, "softmax", torch.softmax, _make_softmax(torch.softmax, False)),
+              (torch.Tensor, "softmax", base.softmax, _make_softmax(base.softmax, False))]
+    if config.flag("VLMC_GELU"):                 # torch's GELU: another instruction sequence in a tensor's last block
+        t.append((F, "gelu", F.gelu, _make_gelu(F.gelu)))
+    if config.flag("VLMC_ROW_MEAN"):             # the fp32 mean inside the norms (batch-variant in torch)
+        t += [(torch, "mean", torch.mean, _make_mean(torch.mean)), (torch.Tensor, "mean", base.mean, _make_mean(base.mean))]
     return t
 
 
@@ -888,36 +886,12 @@ def invariant_matmuls():
         return
     if _mm_depth == 0:
         _mm_owner = _ident()
-        base = torch._C.TensorBase
-        _mm_saved.update(matmul=torch.matmul, bmm=torch.bmm)
-        torch.matmul = _make_matmul(torch.matmul)
-        torch.bmm = _make_matmul(torch.bmm)
-        for name in ("__matmul__", "matmul", "bmm"):              # (inherited from TensorBase: the patch shadows, `del` restores)
-            if name not in torch.Tensor.__dict__:
-                setattr(torch.Tensor, name, _make_matmul(getattr(base, name)))
-                _mm_saved.setdefault("tensor", []).append(name)
-        if os.environ.get("VLMC_SDPA", "1") != "0":               # fused attention written as F.scaled_dot_product_attention
-            import torch.nn.functional as F_
-            _mm_saved["sdpa"] = F_.scaled_dot_product_attention
-            F_.scaled_dot_product_attention = _make_sdpa(F_.scaled_dot_product_attention)
-        if softmax_enabled():                                     # the attention's fp32 softmax: padding-invariant
-            import torch.nn.functional as F_
-            _mm_saved["softmax"] = (F_.softmax, torch.softmax)
-            F_.softmax = _make_softmax(F_.softmax, True)
-            torch.softmax = _make_softmax(torch.softmax, False)
-            if "softmax" not in torch.Tensor.__dict__:
-                setattr(torch.Tensor, "softmax", _make_softmax(base.softmax, False))
-                _mm_saved.setdefault("tensor", []).append("softmax")
-        if os.environ.get("VLMC_GELU", "1") != "0":               # torch's GELU: another instruction sequence in a tensor's last block
-            import torch.nn.functional as F_
-            _mm_saved["gelu"] = F_.gelu
-            F_.gelu = _make_gelu(F_.gelu)
-        if os.environ.get("VLMC_ROW_MEAN", "1") != "0":           # the fp32 mean inside the norms (batch-variant in torch)
-            _mm_saved["mean"] = torch.mean
-            torch.mean = _make_mean(torch.mean)
-            if "mean" not in torch.Tensor.__dict__:
-                setattr(torch.Tensor, "mean", _make_mean(base.mean))
-                _mm_saved.setdefault("tensor", []).append("mean")
+        for owner, name, orig, handler in _function_table():
+            if getattr(owner, name) is not orig:                  # (torch.Tensor's own override of a TensorBase method: left alone)
+                continue
+            # a method torch.Tensor inherits from TensorBase is shadowed by the patch, and `del` restores it
+            _mm_saved.append((owner, name, orig if name in owner.__dict__ else None))
+            setattr(owner, name, handler)
     _mm_depth += 1
     try:
         yield
@@ -926,20 +900,12 @@ def invariant_matmuls():
         if _mm_depth == 0:
             _realize_escaped()
             _mm_owner = None
-            torch.matmul, torch.bmm = _mm_saved.pop("matmul"), _mm_saved.pop("bmm")
-            if "mean" in _mm_saved:
-                torch.mean = _mm_saved.pop("mean")
-            if "gelu" in _mm_saved:
-                import torch.nn.functional as F_
-                F_.gelu = _mm_saved.pop("gelu")
-            if "softmax" in _mm_saved:
-                import torch.nn.functional as F_
-                F_.softmax, torch.softmax = _mm_saved.pop("softmax")
-            if "sdpa" in _mm_saved:
-                import torch.nn.functional as F_
-                F_.scaled_dot_product_attention = _mm_saved.pop("sdpa")
-            for name in _mm_saved.pop("tensor", []):
-                delattr(torch.Tensor, name)
+            while _mm_saved:
+                owner, name, orig = _mm_saved.pop()
+                if orig is None:
+                    delattr(owner, name)
+                else:
+                    setattr(owner, name, orig)
 
 
 # ---- RMS norms of the language-model blocks: one launch instead of seven ------------------------------------------------------
@@ -953,7 +919,7 @@ _NORM_SCAN = weakref.WeakKeyDictionary()      # root module -> its norm candidat
 
 
 def rms_norm_enabled():
-    return os.environ.get("VLMC_RMS_NORM", "1") != "0"
+    return config.flag("VLMC_RMS_NORM")
 
 
 def _norm_eps(m):
@@ -1060,7 +1026,7 @@ def invariant_linears(modules, roots=()):
     norms = []
     try:
         with invariant_matmuls():
-            if roots and rms_norm_enabled() and attn_matmul_enabled() and os.environ.get("VLMC_ROW_MEAN", "1") != "0" \
+            if roots and rms_norm_enabled() and attn_matmul_enabled() and config.flag("VLMC_ROW_MEAN") \
                     and torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
                 for root in roots:
                     for m in _norm_candidates(root):

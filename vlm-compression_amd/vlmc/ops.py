@@ -17,7 +17,7 @@ import threading
 
 import torch
 
-from . import _lib
+from . import _lib, config
 
 _DT = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 
@@ -78,8 +78,7 @@ def _load_fast():
     """The compiled host path (csrc/fastpath/fast_bind.cpp -> vlmc/_fast*.so) for linear_fwd / linear_fwd_group / attn_matmul:
     the same C ABI, ~2 us of host time per call instead of 8-22 through ctypes.  None when it has not been built, when
     `VLMC_FAST=0`, or when `VLMC_LIB` points at another build of the library (the module links the in-tree one)."""
-    import os
-    if os.environ.get("VLMC_FAST", "1") == "0" or os.environ.get("VLMC_LIB"):
+    if not config.flag("VLMC_FAST") or config.text("VLMC_LIB"):
         return None
     try:
         from . import _fast

@@ -6,15 +6,16 @@ synchronisations cost a few percent, which is why the timed steps of the bench n
 from __future__ import annotations
 
 import contextlib
-import os
 import time
+
+from . import config
 
 times: dict = {}
 _stack: list = []
 
 
 def enabled():
-    return os.environ.get("VLMC_PHASE_TIMERS", "0") == "1"
+    return config.flag("VLMC_PHASE_TIMERS")
 
 
 def reset():

@@ -7,7 +7,7 @@ runner_base.py:864-870 aside) and nothing is exchanged.  Capture, replay and eve
 exchange ask this one function, so they cannot disagree about the mode."""
 from __future__ import annotations
 
-import os
+from . import config
 
 
 def simulated_world():
@@ -16,7 +16,7 @@ def simulated_world():
     statistics it fills in W copies of its own rows (same bytes through the same recurrence).  What it measures is a
     rank's floor: everything but the collectives and the other ranks' arrival skew.  0 = off."""
     try:
-        w = int(os.environ.get("VLMC_SIMULATE_WORLD", "0"))
+        w = config.integer("VLMC_SIMULATE_WORLD")
     except ValueError:
         return 0
     if w > 1 and not _warned:
@@ -42,7 +42,7 @@ def require_real_exchange(what):
 def calibration_shard():
     """(rank, world) for sample sharding, or (0, 1) when running as replicas."""
     import torch.distributed as dist
-    if os.environ.get("VLMC_SHARD_CALIB", "1") == "0":
+    if not config.flag("VLMC_SHARD_CALIB"):
         return 0, 1
     if simulated_world():
         return 0, simulated_world()

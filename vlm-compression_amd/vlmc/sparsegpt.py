@@ -22,16 +22,16 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, config
 from . import ops
 from .ops import _need_gpu, _stream
 
 
-_DEFER = __import__("os").environ.get("VLMC_SGPT_DEFER", "1") != "0"
-_SYRK = __import__("os").environ.get("VLMC_SGPT_SYRK", "1") != "0"
+_DEFER = config.flag("VLMC_SGPT_DEFER")
+_SYRK = config.flag("VLMC_SGPT_SYRK")
 # fp32 activations (toy / full-precision models) go as nine bf16 plane products: exact products, but 9x the matrix-core work
 # and a scattering transpose -- measured 48 TFLOP/s-equivalent against 129 for the library's fp32 GEMM, so off by default
-_SYRK_F32 = __import__("os").environ.get("VLMC_SGPT_SYRK_F32", "0") == "1"
+_SYRK_F32 = config.flag("VLMC_SGPT_SYRK_F32")
 _DEFER_BYTES = 256 << 20        # staged activations (as fp32) folded into H once they exceed this
 
 
@@ -136,8 +136,8 @@ def _clamp_inf(H):
 
 
 _CHOL_NB = 128
-_CHOL_PANEL_GEMM = __import__("os").environ.get("VLMC_CHOL_PANEL_GEMM", "1") == "1"   # 0: library triangular solve for the panel
-_CHOL_GRAPH = __import__("os").environ.get("VLMC_CHOL_GRAPH", "1") == "1"
+_CHOL_PANEL_GEMM = config.flag("VLMC_CHOL_PANEL_GEMM")   # 0: library triangular solve for the panel
+_CHOL_GRAPH = config.flag("VLMC_CHOL_GRAPH")
 
 
 def _chol_steps(A, L, inv, info):
@@ -224,13 +224,13 @@ def release_caches():
     _persist_bufs.clear()
 
 
-_SELECT_THRESHOLD = __import__("os").environ.get("VLMC_SGPT_SORT_THRESHOLD", "0") != "1"
+_SELECT_THRESHOLD = not config.flag("VLMC_SGPT_SORT_THRESHOLD")
 factor_stats = {"direct": 0, "chain": 0, "damped": 0}     # how often each route produced the inverse factor (damped: k >= 1 failed attempts, one factorization of H + k damp I)
-_DIRECT_FACTOR = __import__("os").environ.get("VLMC_SGPT_DIRECT_FACTOR", "1") == "1"
+_DIRECT_FACTOR = config.flag("VLMC_SGPT_DIRECT_FACTOR")
 _inv_graphs = {}        # (n, device index, slot) -> (graph, A, L, inv, X, U, info, fork stream)
 # the inverse's rows on a second stream inside the graph (off: measured 3.9 s against 3.2 s per prune -- the cross-stream edges of a
 # captured graph cost more than the two products they take off the critical path)
-_INVERSE_FORK = __import__("os").environ.get("VLMC_SGPT_INVERSE_FORK", "0") == "1"
+_INVERSE_FORK = config.flag("VLMC_SGPT_INVERSE_FORK")
 
 
 def _inverse_factor_steps(A, L, inv, X, U, info, side=None):
@@ -276,9 +276,9 @@ def _inverse_factor_steps(A, L, inv, X, U, info, side=None):
     U.copy_(torch.flip(X, (0, 1)))
 
 
-_PERSISTENT = __import__("os").environ.get("VLMC_SGPT_PERSISTENT", "1") != "0"
+_PERSISTENT = config.flag("VLMC_SGPT_PERSISTENT")
 _persist_bufs = {}      # (n, device index, slot) -> (A, M, X, U, info, workspace)
-PERSISTENT_MAX_WORKGROUPS = int(__import__("os").environ.get("VLMC_SGPT_PERSISTENT_WGS", "128"))
+PERSISTENT_MAX_WORKGROUPS = config.integer("VLMC_SGPT_PERSISTENT_WGS")
 
 
 def persistent_factor_usable(n: int) -> bool:
@@ -372,7 +372,7 @@ _SWEEP_STREAMS = {}        # device index -> side streams for the column sweeps 
 
 def sweep_streams(dev):
     """Side streams for the sweeps of a block's linears (`VLMC_SGPT_SWEEP_STREAMS=n`, default 4; 1: none)."""
-    n = int(__import__("os").environ.get("VLMC_SGPT_SWEEP_STREAMS", "4"))
+    n = config.integer("VLMC_SGPT_SWEEP_STREAMS")
     if n <= 1:
         return []
     sts = _SWEEP_STREAMS.setdefault(dev.index, [])
@@ -383,7 +383,7 @@ def sweep_streams(dev):
 
 def concurrent_factor_enabled():
     """`VLMC_SGPT_CONCURRENT=0`: the Hessians of a block are factorized one after the other, each with its own host checks."""
-    return __import__("os").environ.get("VLMC_SGPT_CONCURRENT", "1") != "0"
+    return config.flag("VLMC_SGPT_CONCURRENT")
 
 
 @torch.no_grad()
@@ -582,7 +582,7 @@ def trailing_update(W: torch.Tensor, c0: int, c1: int, err: torch.Tensor, U: tor
         U.data_ptr() + (i1 * U.stride(0) + c0) * el, U.stride(0), i2 - i1, _stream()))
 
 
-_BLOCK_LOOP = __import__("os").environ.get("VLMC_SGPT_BLOCK_LOOP", "1") != "0"     # 0: the block loop issued from Python, launch by launch (the cross-check)
+_BLOCK_LOOP = config.flag("VLMC_SGPT_BLOCK_LOOP")     # 0: the block loop issued from Python, launch by launch (the cross-check)
 
 
 def prune_blocks(W: torch.Tensor, U: torch.Tensor, blocksize: int, prune_n: int, prune_m: int, rows_per_scope=None, sparsities=None,
@@ -611,7 +611,7 @@ def prune_blocks(W: torch.Tensor, U: torch.Tensor, blocksize: int, prune_n: int,
         mask_out.stride(0) if mask_out is not None else 0, ws.data_ptr() if ws is not None else None, _stream()))
 
 
-_SELECT_SWEEP = __import__("os").environ.get("VLMC_SGPT_SELECT_SWEEP", "1") != "0"
+_SELECT_SWEEP = config.flag("VLMC_SGPT_SELECT_SWEEP")
 _select_ws = {}            # device index -> the zero-filled workspace of vlmc_sparsegpt_select_sweep (returned zero by every call)
 _sweep_rows = {}          # device index -> rows the one-launch threshold + sweep takes on that part
 
@@ -711,7 +711,7 @@ def fasterprune(layer, H: torch.Tensor, sparsity, prune_n=0, prune_m=0, blocksiz
 
 def stacked_sweeps_enabled():
     """`VLMC_SGPT_STACK=0`: every linear runs its own column sweep (the reference's loop, one linear at a time)."""
-    return __import__("os").environ.get("VLMC_SGPT_STACK", "1") != "0"
+    return config.flag("VLMC_SGPT_STACK")
 
 
 @torch.no_grad()
