@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VLMC_ABI_VERSION 20
+#define VLMC_ABI_VERSION 21
 
 #define VLMC_OK 0
 #define VLMC_EINVAL (-1)     /* bad argument (shape, dtype, alignment, null pointer) */
@@ -47,6 +47,12 @@ extern "C" {
 #define VLMC_SEL_ROW 0    /* per output row, k smallest, stable (wanda_pruner.py:332-337) */
 #define VLMC_SEL_MATRIX 1 /* matrix-wide strict threshold (wanda_pruner.py:682-683)      */
 #define VLMC_SEL_NM 2     /* n of every m consecutive columns (wanda_pruner.py:326-329)  */
+
+/* DSnoT initial metrics (`initial_method`, dsnot_pruner.py:371-402) */
+#define VLMC_DSNOT_INIT_MAGNITUDE 0 /* |w|                                                          (:378)     */
+#define VLMC_DSNOT_INIT_WANDA 1     /* |w| * sqrt(scaler_row)[c]                                    (:373-376) */
+#define VLMC_DSNOT_INIT_SPARSEGPT 2 /* fp32(fp32(w*w) / diag(U)[c]), U = cholesky(cholesky_inverse(cholesky(H + damp I)),
+                                       upper); a dead column (diag(H) == 0) has divisor +inf and metric 0 (:380-402) */
 
 int vlmc_abi_version(void);
 const char *vlmc_last_error(void);
@@ -507,6 +513,27 @@ int vlmc_dsnot_refine(const void *W, int dtype, int64_t out_features, int64_t in
                       int without_same_sign, uint32_t *events, int32_t *stop_cycle, void *stream);
 int vlmc_dsnot_apply(void *W, int dtype, int64_t out_features, int64_t in_features, int64_t ldw, uint8_t *keep_mask,
                      const uint32_t *events, const int32_t *ncycles, int max_cycle, int nm_mode, int apply_zero, void *stream);
+
+/* vlmc_dsnot_initial_select: DSnoT's initial mask with the metric of `init_kind` (dsnot_pruner.py:371-402): mode VLMC_SEL_ROW
+ *   prunes the k smallest (metric, column) of every row -- the stable sort of :555-560, k = round(in * ratio) -- and
+ *   VLMC_SEL_NM n of every m (:420-430, ties as vlmc_wanda_select's SEL_NM).  keep_mask (1 = keep) only: W is not written.
+ *   column_table: sqrt(scaler_row) for VLMC_DSNOT_INIT_WANDA (a unit table gives the magnitude metric -- exactly the
+ *   vlmc_wanda_select kernels), the divisor diag(U) (+inf = dead column) for VLMC_DSNOT_INIT_SPARSEGPT.  The fp32 metric is
+ *   formed in registers, never stored.  in_features <= 16384 and a multiple of 8 (and of m), 16-byte aligned W rows and table.
+ * vlmc_dsnot_refine_kind: vlmc_dsnot_refine with the initial metric chosen by init_kind; it is read where the reference reads
+ *   `initial_metric` in the cycles (n:m :469-529); the unstructured cycles' prune lists use |w| * sqrt_scaler whatever the
+ *   kind (:583-590).  init_div: the SPARSEGPT divisor (required for that kind, ignored otherwise).  vlmc_dsnot_refine is this
+ *   call with init_kind = use_wanda_init ? VLMC_DSNOT_INIT_WANDA : VLMC_DSNOT_INIT_MAGNITUDE.
+ * vlmc_dsnot_divisor: div[c] = dead[c] ? +inf : U[c, c] for the upper factor U (row stride ldu) of (H + damp I)^-1 and the
+ *   dead-column bytes of H (diag(H) == 0 before it was filled, :382-385).                                                   */
+int vlmc_dsnot_initial_select(const void *W, int dtype, int64_t out_features, int64_t in_features, int64_t ldw,
+                              const float *column_table, int init_kind, int mode, int64_t k, int n, int m, uint8_t *keep_mask,
+                              void *stream);
+int vlmc_dsnot_refine_kind(const void *W, int dtype, int64_t out_features, int64_t in_features, int64_t ldw,
+                           const uint8_t *keep_mask0, const float *sqrt_scaler, const float *sum_row, const float *var_row,
+                           int init_kind, const float *init_div, int prune_n, int prune_m, int max_cycle, float update_threshold,
+                           float pow_of_var, int without_same_sign, uint32_t *events, int32_t *stop_cycle, void *stream);
+int vlmc_dsnot_divisor(const float *U, int64_t n, int64_t ldu, const uint8_t *dead, float *div, void *stream);
 
 /* vlmc_reorder_indices: `return_reorder_indice(input_tensor)` (dsnot_pruner.py:1881-1925), the module-level helper the
  *   unstructured branch orders its prune list with (:623-631).  Per row of x [rows, cols] (row stride ldx; VLMC_F32 / F16 / BF16):

@@ -105,6 +105,17 @@ __device__ __forceinline__ float ieee_div(float a, float b) { return a / b; }
 __device__ __forceinline__ float ieee_mul(float a, float b) { return a * b; }
 __device__ __forceinline__ float ieee_add(float a, float b) { return a + b; }
 
+// DSnoT's initial metric per element (dsnot_pruner.py:371-402), by kind (include/vlmc.h VLMC_DSNOT_INIT_*):
+// magnitude |w|; wanda |w| * sqrt(scaler_row)[c]; sparsegpt fp32(w*w) / diag(U)[c] with +inf in div[c] for a dead
+// column (the reference zeroes it in its copy of W: metric 0).
+__device__ __forceinline__ float dsnot_init_metric(int kind, float w, const float *sq, const float *div, int64_t c) {
+    if (kind == VLMC_DSNOT_INIT_SPARSEGPT) {
+        const float d = div[c];
+        return d == __builtin_inff() ? 0.f : ieee_div(ieee_mul(w, w), d);
+    }
+    return kind == VLMC_DSNOT_INIT_WANDA ? ieee_mul(fabsf(w), sq[c]) : fabsf(w);
+}
+
 constexpr int kWave = 64;
 
 // wave-wide sum of a 32-bit integer (result valid in every lane)

@@ -194,7 +194,7 @@ __device__ __forceinline__ Best block_best(Best v, bool take_min, DsSmem<NW> &sm
 template <typename T, int CH, int NW, bool NM>
 __global__ __launch_bounds__(64 * NW) void dsnot_simulate_kernel(
     const typename T::raw *__restrict__ W, int64_t out_f, int64_t in_f, int64_t ldw, const uint8_t *__restrict__ keep0,
-    const float *__restrict__ sqrt_scaler, const float *__restrict__ sum_row, const float *__restrict__ var_row, int use_wanda_init,
+    const float *__restrict__ sqrt_scaler, const float *__restrict__ sum_row, const float *__restrict__ var_row, int init_kind, const float *__restrict__ init_div,
     int prune_m, int max_cycle, float thr, float pow_var, int without_same_sign, uint32_t *__restrict__ events,
     int32_t *__restrict__ t_row) {
     constexpr int NT = 64 * NW, E = CH * 8;
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(64 * NW) void dsnot_simulate_kernel(
                 live |= 1u << i;
                 if (pr) pruned0 |= 1u << i;
                 // metric used to order the kept columns / pick the group minimum
-                const float init = use_wanda_init ? ieee_mul(fabsf(w), sqrt_scaler[col0 + j]) : fabsf(w);
+                const float init = dsnot_init_metric(init_kind, w, sqrt_scaler, init_div, col0 + j);
                 const float wanda = NM ? init : ieee_mul(fabsf(w), sqrt_scaler[col0 + j]);
                 wk[i] = score_key(wanda);
                 float g = pr ? d : 0.f;
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(256) void dsnot_apply_kernel(typename T::raw *__res
 // ------------------------------------------------------------------------------------------
 template <typename T, bool NM>
 static int simulate_dispatch(const void *W, int64_t out_f, int64_t in_f, int64_t ldw, const uint8_t *keep0, const float *sq,
-                             const float *sum_row, const float *var_row, int use_wanda_init, int prune_m, int max_cycle,
+                             const float *sum_row, const float *var_row, int init_kind, const float *init_div, int prune_m, int max_cycle,
                              float thr, float pow_var, int without_same_sign, uint32_t *events, int32_t *t_row, hipStream_t st) {
     using raw = typename T::raw;
     const int64_t nchunks = in_f / 8;
@@ -517,7 +517,7 @@ static int simulate_dispatch(const void *W, int64_t out_f, int64_t in_f, int64_t
     const int ch = int((nchunks + 64 * nw - 1) / (64 * nw));
 #define VLMC_SIM(CH, NW)                                                                                                  \
     hipLaunchKernelGGL((dsnot_simulate_kernel<T, CH, NW, NM>), dim3(unsigned(out_f)), dim3(64 * NW), 0, st,                \
-                       static_cast<const raw *>(W), out_f, in_f, ldw, keep0, sq, sum_row, var_row, use_wanda_init, prune_m, \
+                       static_cast<const raw *>(W), out_f, in_f, ldw, keep0, sq, sum_row, var_row, init_kind, init_div, prune_m, \
                        max_cycle, thr, pow_var, without_same_sign, events, t_row)
 #define VLMC_SIM_NW(NW)                     \
     switch (ch) {                           \
@@ -542,7 +542,7 @@ static int simulate_dispatch(const void *W, int64_t out_f, int64_t in_f, int64_t
 
 namespace vlmc {
 int dsnot_refine_lists(const void *W, int dtype, int64_t out_f, int64_t in_f, int64_t ldw, const uint8_t *keep0, const float *sq,
-                       const float *sum_row, const float *var_row, int use_wanda_init, int prune_n, int prune_m, int max_cycle,
+                       const float *sum_row, const float *var_row, int init_kind, const float *init_div, int prune_n, int prune_m, int max_cycle,
                        float thr, float pow_var, int without_same_sign, uint32_t *events, int32_t *t_row, hipStream_t st);
 }
 using namespace vlmc;
@@ -583,11 +583,19 @@ extern "C" int vlmc_dsnot_stats_update(float *scaler_row, float *sum_row, float 
     return VLMC_OK;
 }
 
-extern "C" int vlmc_dsnot_refine(const void *W, int dtype, int64_t out_features, int64_t in_features, int64_t ldw,
-                                 const uint8_t *keep_mask0, const float *sqrt_scaler, const float *sum_row, const float *var_row,
-                                 int use_wanda_init, int prune_n, int prune_m, int max_cycle, float update_threshold,
-                                 float pow_of_var, int without_same_sign, uint32_t *events, int32_t *stop_cycle, void *stream) {
+extern "C" int vlmc_dsnot_refine_kind(const void *W, int dtype, int64_t out_features, int64_t in_features, int64_t ldw,
+                                      const uint8_t *keep_mask0, const float *sqrt_scaler, const float *sum_row, const float *var_row,
+                                      int init_kind, const float *init_div, int prune_n, int prune_m, int max_cycle,
+                                      float update_threshold, float pow_of_var, int without_same_sign, uint32_t *events,
+                                      int32_t *stop_cycle, void *stream) {
     VLMC_REQUIRE(W && keep_mask0 && sqrt_scaler && sum_row && var_row && events && stop_cycle, "vlmc_dsnot_refine: null pointer");
+    VLMC_REQUIRE(init_kind == VLMC_DSNOT_INIT_MAGNITUDE || init_kind == VLMC_DSNOT_INIT_WANDA || init_kind == VLMC_DSNOT_INIT_SPARSEGPT,
+                 "vlmc_dsnot_refine_kind: unknown init_kind %d", init_kind);
+    VLMC_REQUIRE(init_kind != VLMC_DSNOT_INIT_SPARSEGPT || init_div, "vlmc_dsnot_refine_kind: the sparsegpt kind needs a divisor");
+    VLMC_REQUIRE(in_features <= 16384, "vlmc_dsnot_refine: in_features %lld too large (max 16384)", (long long)in_features);
+    if (prune_n != 0)
+        VLMC_REQUIRE(prune_m > 0 && in_features % prune_m == 0, "vlmc_dsnot_refine: in_features %lld not a multiple of m=%d",
+                     (long long)in_features, prune_m);
     VLMC_REQUIRE(out_features > 0 && in_features > 0 && in_features % 8 == 0 && ldw % 8 == 0 && aligned16(W) &&
                      (reinterpret_cast<uintptr_t>(keep_mask0) % 8) == 0,
                  "vlmc_dsnot_refine: needs in_features %% 8 == 0 and 16-byte aligned rows (in=%lld)", (long long)in_features);
@@ -598,7 +606,7 @@ extern "C" int vlmc_dsnot_refine(const void *W, int dtype, int64_t out_features,
     // fast path: sorted-list heads + O(1) cycles (dsnot_lists.hip); VLMC_DSNOT_LISTS=0 keeps the per-cycle reductions
     if (env_flag("VLMC_DSNOT_LISTS", true)) {
         const int rc = dsnot_refine_lists(W, dtype, out_features, in_features, ldw, keep_mask0, sqrt_scaler, sum_row, var_row,
-                                          use_wanda_init, prune_n, prune_m, max_cycle, update_threshold, pow_of_var,
+                                          init_kind, init_div, prune_n, prune_m, max_cycle, update_threshold, pow_of_var,
                                           without_same_sign, events, stop_cycle, st);
         if (rc == VLMC_OK) {
             VLMC_HIP_CHECK_LAUNCH("vlmc_dsnot_refine");
@@ -607,10 +615,10 @@ extern "C" int vlmc_dsnot_refine(const void *W, int dtype, int64_t out_features,
     }
 #define VLMC_DS(T)                                                                                                              \
     (prune_n != 0 ? simulate_dispatch<T, true>(W, out_features, in_features, ldw, keep_mask0, sqrt_scaler, sum_row, var_row,     \
-                                               use_wanda_init, prune_m, max_cycle, update_threshold, pow_of_var,                 \
+                                               init_kind, init_div, prune_m, max_cycle, update_threshold, pow_of_var,                 \
                                                without_same_sign, events, stop_cycle, st)                                        \
                   : simulate_dispatch<T, false>(W, out_features, in_features, ldw, keep_mask0, sqrt_scaler, sum_row, var_row,    \
-                                                use_wanda_init, prune_m, max_cycle, update_threshold, pow_of_var,                \
+                                                init_kind, init_div, prune_m, max_cycle, update_threshold, pow_of_var,                \
                                                 without_same_sign, events, stop_cycle, st))
     switch (dtype) {
         case VLMC_F32: return VLMC_DS(f32_t);
@@ -620,6 +628,16 @@ extern "C" int vlmc_dsnot_refine(const void *W, int dtype, int64_t out_features,
 #undef VLMC_DS
     set_error("vlmc_dsnot_refine: unknown dtype %d", dtype);
     return VLMC_EINVAL;
+}
+
+// the ABI-20 entry point: use_wanda_init != 0 is the Wanda kind, 0 the magnitude kind
+extern "C" int vlmc_dsnot_refine(const void *W, int dtype, int64_t out_features, int64_t in_features, int64_t ldw,
+                                 const uint8_t *keep_mask0, const float *sqrt_scaler, const float *sum_row, const float *var_row,
+                                 int use_wanda_init, int prune_n, int prune_m, int max_cycle, float update_threshold,
+                                 float pow_of_var, int without_same_sign, uint32_t *events, int32_t *stop_cycle, void *stream) {
+    return vlmc_dsnot_refine_kind(W, dtype, out_features, in_features, ldw, keep_mask0, sqrt_scaler, sum_row, var_row,
+                                  use_wanda_init ? VLMC_DSNOT_INIT_WANDA : VLMC_DSNOT_INIT_MAGNITUDE, nullptr, prune_n, prune_m,
+                                  max_cycle, update_threshold, pow_of_var, without_same_sign, events, stop_cycle, stream);
 }
 
 extern "C" int vlmc_dsnot_apply(void *W, int dtype, int64_t out_features, int64_t in_features, int64_t ldw, uint8_t *keep_mask,
@@ -697,5 +715,22 @@ extern "C" int vlmc_reorder_indices(const void *x, int dtype, int64_t rows, int6
     }
 #undef VLMC_RO
     VLMC_HIP_CHECK_LAUNCH("vlmc_reorder_indices");
+    return VLMC_OK;
+}
+
+// ---- vlmc_dsnot_divisor: the SparseGPT initial metric's per-column divisor, on the device (no host round trip per linear) ----
+namespace vlmc {
+__global__ __launch_bounds__(256) void dsnot_divisor_kernel(const float *__restrict__ U, int64_t n, int64_t ldu,
+                                                            const uint8_t *__restrict__ dead, float *__restrict__ div) {
+    const int64_t c = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (c < n) div[c] = dead[c] ? __builtin_inff() : U[c * ldu + c];
+}
+}  // namespace vlmc
+
+extern "C" int vlmc_dsnot_divisor(const float *U, int64_t n, int64_t ldu, const uint8_t *dead, float *div, void *stream) {
+    VLMC_REQUIRE(U && dead && div, "vlmc_dsnot_divisor: null pointer");
+    VLMC_REQUIRE(n > 0 && n <= 16384 && ldu >= n, "vlmc_dsnot_divisor: bad shape n=%lld ldu=%lld", (long long)n, (long long)ldu);
+    hipLaunchKernelGGL(dsnot_divisor_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, as_stream(stream), U, n, ldu, dead, div);
+    VLMC_HIP_CHECK_LAUNCH("vlmc_dsnot_divisor");
     return VLMC_OK;
 }

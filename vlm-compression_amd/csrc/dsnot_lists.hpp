@@ -550,7 +550,7 @@ template <typename T, int CH, int NW, bool NM>
 // wider forms reach 4: the attribute states what each instantiation achieves)
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW == 1 || (NM && NW == 2)) ? 3 : 4))) void dsnot_lists_kernel(
     const typename T::raw *__restrict__ W, int64_t out_f, int64_t in_f, int64_t ldw, const uint8_t *__restrict__ keep0,
-    const float *__restrict__ sqrt_scaler, const float *__restrict__ sum_row, const float *__restrict__ var_row, int use_wanda_init,
+    const float *__restrict__ sqrt_scaler, const float *__restrict__ sum_row, const float *__restrict__ var_row, int init_kind, const float *__restrict__ init_div,
     int prune_m, int max_cycle, float thr, float pow_var, int without_same_sign, uint32_t *__restrict__ events,
     int32_t *__restrict__ t_row, int fast) {
     constexpr int NT = 64 * NW, E = CH * 8;
@@ -643,7 +643,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW == 
                 const uint32_t c = in ? g0 + uint32_t(a) : g0;
                 const float w = to_f32<T>(wrow[c]);
                 d[a] = ieee_mul(w, sum_row[c]);
-                key[a] = score_key(use_wanda_init ? ieee_mul(fabsf(w), sqrt_scaler[c]) : fabsf(w));
+                key[a] = score_key(dsnot_init_metric(init_kind, w, sqrt_scaler, init_div, c));
                 kept[a] = in && krow[c] != 0;
             }
             // visit v takes what `torch.topk(block, 1, largest=False)` returns for the group's current metrics (:517-519) -- kept
@@ -834,7 +834,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW == 
 
 template <typename T, bool NM>
 static int lists_dispatch(const void *W, int64_t out_f, int64_t in_f, int64_t ldw, const uint8_t *keep0, const float *sq,
-                          const float *sum_row, const float *var_row, int use_wanda_init, int prune_m, int max_cycle,
+                          const float *sum_row, const float *var_row, int init_kind, const float *init_div, int prune_m, int max_cycle,
                           float thr, float pow_var, int without_same_sign, uint32_t *events, int32_t *t_row, hipStream_t st) {
     using raw = typename T::raw;
     const int64_t nchunks = in_f / 8;
@@ -851,7 +851,7 @@ static int lists_dispatch(const void *W, int64_t out_f, int64_t in_f, int64_t ld
     const int fast = env_flag("VLMC_DSNOT_RADIX_ONLY", false) ? 0 : 1;   // the exact route alone (tests compare the two)
 #define VLMC_DL(CH, NW)                                                                                                    \
     hipLaunchKernelGGL((dsnot_lists_kernel<T, CH, NW, NM>), dim3(unsigned(out_f)), dim3(64 * NW), 0, st,                    \
-                       static_cast<const raw *>(W), out_f, in_f, ldw, keep0, sq, sum_row, var_row, use_wanda_init, prune_m, \
+                       static_cast<const raw *>(W), out_f, in_f, ldw, keep0, sq, sum_row, var_row, init_kind, init_div, prune_m, \
                        max_cycle, thr, pow_var, without_same_sign, events, t_row, fast)
 #define VLMC_DL_NW(NW) do { if (ch == 2) VLMC_DL(2, NW); else VLMC_DL(4, NW); } while (0)
     switch (nw) {
@@ -876,15 +876,15 @@ static int lists_dispatch(const void *W, int64_t out_f, int64_t in_f, int64_t ld
 
 template <bool NM>
 static int lists_dispatch_dtype(const void *W, int dtype, int64_t out_f, int64_t in_f, int64_t ldw, const uint8_t *keep0,
-                                const float *sq, const float *sum_row, const float *var_row, int use_wanda_init, int prune_m,
+                                const float *sq, const float *sum_row, const float *var_row, int init_kind, const float *init_div, int prune_m,
                                 int max_cycle, float thr, float pow_var, int without_same_sign, uint32_t *events, int32_t *t_row,
                                 hipStream_t st) {
     switch (dtype) {
-        case VLMC_F32: return lists_dispatch<f32_t, NM>(W, out_f, in_f, ldw, keep0, sq, sum_row, var_row, use_wanda_init, prune_m,
+        case VLMC_F32: return lists_dispatch<f32_t, NM>(W, out_f, in_f, ldw, keep0, sq, sum_row, var_row, init_kind, init_div, prune_m,
                                                         max_cycle, thr, pow_var, without_same_sign, events, t_row, st);
-        case VLMC_F16: return lists_dispatch<f16_t, NM>(W, out_f, in_f, ldw, keep0, sq, sum_row, var_row, use_wanda_init, prune_m,
+        case VLMC_F16: return lists_dispatch<f16_t, NM>(W, out_f, in_f, ldw, keep0, sq, sum_row, var_row, init_kind, init_div, prune_m,
                                                         max_cycle, thr, pow_var, without_same_sign, events, t_row, st);
-        case VLMC_BF16: return lists_dispatch<bf16_t, NM>(W, out_f, in_f, ldw, keep0, sq, sum_row, var_row, use_wanda_init, prune_m,
+        case VLMC_BF16: return lists_dispatch<bf16_t, NM>(W, out_f, in_f, ldw, keep0, sq, sum_row, var_row, init_kind, init_div, prune_m,
                                                           max_cycle, thr, pow_var, without_same_sign, events, t_row, st);
     }
     return VLMC_EINVAL;

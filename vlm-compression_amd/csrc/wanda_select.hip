@@ -153,6 +153,17 @@ __device__ __forceinline__ int find_job(const SelBatch &b, uint32_t unit, uint32
 }
 
 // ------------------------------------------------------------------------------------------
+// score of one element.  MK = kMetricWanda: |w| * sqrt(scaler) (the table holds sqrt(scaler_row); magnitude = a unit table).
+// MK = kMetricSaliency: DSnoT's SparseGPT initial metric fp32(fp32(w*w) / diag(U)[c]) (dsnot_pruner.py:382-402), the table
+// holds diag(U); a dead column (diag(H) == 0, zeroed in the reference's copy of W) is encoded as +inf and scores 0.
+// ------------------------------------------------------------------------------------------
+constexpr int kMetricWanda = 0, kMetricSaliency = 1;
+template <int MK> __device__ __forceinline__ float sel_score(float w, float s) {
+    if constexpr (MK == kMetricWanda) return ieee_mul(fabsf(w), s);
+    else return s == __builtin_inff() ? 0.f : ieee_div(ieee_mul(w, w), s);
+}
+
+// ------------------------------------------------------------------------------------------
 // SEL_ROW: one workgroup of NW waves per row, grid = rows (the hardware dispatcher overlaps
 // rows that are loading, searching and storing on every SIMD).
 //
@@ -229,7 +240,7 @@ template <int NW> __device__ __forceinline__ void row_sync() {
 }
 
 // One row by the NW waves whose lanes are numbered `tid` = 0 .. 64*NW-1 and who own `sm`.
-template <typename T, int CH, int NW, bool ALIGNED>
+template <typename T, int CH, int NW, bool ALIGNED, int MK = kMetricWanda>
 __device__ __forceinline__ void select_row_body(const SelBatch &b, const SelJob &jb, const uint32_t row32, RowSmem<NW> &sm,
                                                 const int tid) {
     constexpr int NT = 64 * NW;
@@ -270,7 +281,7 @@ __device__ __forceinline__ void select_row_body(const SelBatch &b, const SelJob 
         for (int j = 0; j < 8; ++j) {
             const bool live = valid[s] && (ALIGNED || col0 + j < in_f);
             if (live) {
-                const float sc = ieee_mul(fabsf(to_f32<T>(raw[s].v[j])), sq[j]);
+                const float sc = sel_score<MK>(to_f32<T>(raw[s].v[j]), sq[j]);
                 // score >= +0 or NaN; every NaN -> one key above +inf (torch.sort puts NaN last)
                 const uint32_t b = __float_as_uint(sc);
                 key[s * 8 + j] = b < 0x7F800001u ? b : 0x7F800001u;
@@ -487,13 +498,13 @@ __device__ __forceinline__ void select_row_body(const SelBatch &b, const SelJob 
 #endif
 }
 
-template <typename T, int CH, int NW, bool ALIGNED>
+template <typename T, int CH, int NW, bool ALIGNED, int MK = kMetricWanda>
 __global__ __launch_bounds__(64 * NW, (NW * CH >= 4 && CH >= 3) ? 5 : 8)
 void select_rows_kernel(const SelBatch b) {
     __shared__ RowSmem<NW> sm;
     uint32_t row32;
     const SelJob &jb = b.job[find_job(b, blockIdx.x, row32)];
-    select_row_body<T, CH, NW, ALIGNED>(b, jb, row32, sm, int(threadIdx.x));
+    select_row_body<T, CH, NW, ALIGNED, MK>(b, jb, row32, sm, int(threadIdx.x));
 }
 
 // Rows of two widths in ONE grid of 4-wave workgroups (a T5 block: the 2048-wide rows of q/k/v/o/wi and the
@@ -1493,7 +1504,7 @@ __global__ __launch_bounds__(1024, 1) void matrix_fused_kernel(const SelBatch b)
 // ------------------------------------------------------------------------------------------
 // SEL_NM
 // ------------------------------------------------------------------------------------------
-template <typename T, bool ALIGNED, int M>
+template <typename T, bool ALIGNED, int M, int MK = kMetricWanda>
 __global__ __launch_bounds__(256) void nm_kernel(const SelBatch b) {
     __shared__ double dsm[4];
     uint32_t wg;
@@ -1513,7 +1524,7 @@ __global__ __launch_bounds__(256) void nm_kernel(const SelBatch b) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             if (ALIGNED || col0 + j < in_f) {
-                const float sc = ieee_mul(fabsf(to_f32<T>(raw.v[j])), sqv[j]);
+                const float sc = sel_score<MK>(to_f32<T>(raw.v[j]), sqv[j]);
                 fs += sc;
                 key[j] = score_key(sc);
             } else {
@@ -1593,7 +1604,7 @@ static void fill_job(SelJob &d, const vlmc_select_job &j) {
 
 // (NW waves) x (CH chunks of 8 columns per lane) must cover the row: 64*NW*CH >= in/8.
 // Few rows -> more waves per row (parallelism); many rows -> one wave per row (no barriers).
-template <typename T>
+template <typename T, int MK = kMetricWanda>
 static int launch_rows(const vlmc_select_job *jobs, const int *idx, int n, int apply_zero, hipStream_t st) {
     const vlmc_select_job &j0 = jobs[idx[0]];
     const int64_t in_f = j0.in_features, nchunks = (in_f + 7) / 8;
@@ -1614,11 +1625,16 @@ static int launch_rows(const vlmc_select_job *jobs, const int *idx, int n, int a
     }
     const bool aligned = job_aligned(j0);
 #define VLMC_ROWS(CH, NW, AL) \
-    VLMC_LAUNCH_TIMED((select_rows_kernel<T, CH, NW, AL>), dim3(unsigned(rows)), dim3(64 * NW), st, b)
+    VLMC_LAUNCH_TIMED((select_rows_kernel<T, CH, NW, AL, MK>), dim3(unsigned(rows)), dim3(64 * NW), st, b)
     if (!aligned) {
-        if (nchunks <= 256) VLMC_ROWS(4, 1, false);
-        else VLMC_ROWS(4, 8, false);
-        return VLMC_OK;
+        if constexpr (MK != kMetricWanda) {                          // (the saliency entry point requires aligned rows)
+            set_error("vlmc_dsnot_initial_select: needs 16-byte aligned rows and in_features %% 8 == 0");
+            return VLMC_EINVAL;
+        } else {
+            if (nchunks <= 256) VLMC_ROWS(4, 1, false);
+            else VLMC_ROWS(4, 8, false);
+            return VLMC_OK;
+        }
     }
     int nw = 1;
     while (nw < 8 && nchunks > int64_t(64) * nw * 4) nw *= 2;               // CH <= 4
@@ -1763,7 +1779,7 @@ static int launch_matrix(const vlmc_select_job *jobs, const int *idx, int n, int
     return VLMC_OK;
 }
 
-template <typename T>
+template <typename T, int MK = kMetricWanda>
 static int launch_nm(const vlmc_select_job *jobs, const int *idx, int n, int prune_n, int prune_m, int apply_zero,
                      hipStream_t st) {
     SelBatch b;
@@ -1780,8 +1796,9 @@ static int launch_nm(const vlmc_select_job *jobs, const int *idx, int n, int pru
     }
 #define VLMC_NM(M)                                                                                         \
     do {                                                                                                   \
-        if (aligned) hipLaunchKernelGGL((nm_kernel<T, true, M>), dim3(wgs), dim3(256), 0, st, b);          \
-        else hipLaunchKernelGGL((nm_kernel<T, false, M>), dim3(wgs), dim3(256), 0, st, b);                 \
+        if (aligned) hipLaunchKernelGGL((nm_kernel<T, true, M, MK>), dim3(wgs), dim3(256), 0, st, b);      \
+        else if constexpr (MK == kMetricWanda) hipLaunchKernelGGL((nm_kernel<T, false, M>), dim3(wgs), dim3(256), 0, st, b); \
+        else { set_error("vlmc_dsnot_initial_select: needs 16-byte aligned rows"); return VLMC_EINVAL; }  \
     } while (0)
     switch (prune_m) {
         case 2: VLMC_NM(2); break;
@@ -1892,4 +1909,48 @@ extern "C" int vlmc_wanda_select(void *W, int dtype, int64_t out_features, int64
     const vlmc_select_job j{W, out_features, in_features, ldw, sqrt_scaler, k, mask, score_partials, workspace,
                             workspace_bytes};
     return vlmc_wanda_select_batch(&j, 1, dtype, mode, n, m, apply_zero, stream);
+}
+
+// ---- vlmc_dsnot_initial_select: DSnoT's initial mask (dsnot_pruner.py:371-430 / :555-560) with the metric of `init_kind` ----------
+// The SEL_ROW / SEL_NM kernels above with the score chosen at compile time; the fp32 metric lives in registers only.  Masks only
+// (apply_zero = 0, no score partials): DSnoT zeroes the weights after its cycles (vlmc_dsnot_apply).
+extern "C" int vlmc_dsnot_initial_select(const void *W, int dtype, int64_t out_features, int64_t in_features, int64_t ldw,
+                                         const float *column_table, int init_kind, int mode, int64_t k, int n, int m,
+                                         uint8_t *keep_mask, void *stream) {
+    VLMC_REQUIRE(W && column_table && keep_mask, "vlmc_dsnot_initial_select: null pointer");
+    VLMC_REQUIRE(init_kind == VLMC_DSNOT_INIT_WANDA || init_kind == VLMC_DSNOT_INIT_SPARSEGPT,
+                 "vlmc_dsnot_initial_select: unknown init_kind %d (magnitude = VLMC_DSNOT_INIT_WANDA with a unit table)", init_kind);
+    VLMC_REQUIRE(mode == VLMC_SEL_ROW || mode == VLMC_SEL_NM, "vlmc_dsnot_initial_select: mode %d is neither SEL_ROW nor SEL_NM", mode);
+    VLMC_REQUIRE(out_features > 0 && in_features > 0 && in_features <= 16384 && ldw >= in_features && ldw < (int64_t(1) << 32) &&
+                     out_features * in_features < (int64_t(1) << 32),
+                 "vlmc_dsnot_initial_select: bad shape out=%lld in=%lld ldw=%lld (in_features <= 16384)", (long long)out_features,
+                 (long long)in_features, (long long)ldw);
+    VLMC_REQUIRE(in_features % 8 == 0 && ldw % 8 == 0 && aligned16(W) && aligned16(column_table) &&
+                     (reinterpret_cast<uintptr_t>(keep_mask) % 8) == 0,
+                 "vlmc_dsnot_initial_select: needs in_features %% 8 == 0 and 16-byte aligned rows / table");
+    if (mode == VLMC_SEL_ROW)
+        VLMC_REQUIRE(k >= 0 && k <= in_features, "vlmc_dsnot_initial_select: row k=%lld outside [0,%lld]", (long long)k,
+                     (long long)in_features);
+    else
+        VLMC_REQUIRE((m == 2 || m == 4 || m == 8) && n >= 0 && n <= m && in_features % m == 0,
+                     "vlmc_dsnot_initial_select: bad n:m = %d:%d for in_features %lld", n, m, (long long)in_features);
+    if (init_kind == VLMC_DSNOT_INIT_WANDA)                   // the Wanda kernels, exactly (vlmc_wanda_select with apply_zero = 0)
+        return vlmc_wanda_select(const_cast<void *>(W), dtype, out_features, in_features, ldw, column_table, mode, k, n, m, 0,
+                                 keep_mask, nullptr, nullptr, 0, stream);
+    const vlmc_select_job j{const_cast<void *>(W), out_features, in_features, ldw, column_table, k, keep_mask, nullptr, nullptr, 0};
+    const int idx[1] = {0};
+    hipStream_t st = as_stream(stream);
+    int rc;
+#define VLMC_IS(T) (mode == VLMC_SEL_ROW ? launch_rows<T, kMetricSaliency>(&j, idx, 1, 0, st)                    \
+                                         : launch_nm<T, kMetricSaliency>(&j, idx, 1, n, m, 0, st))
+    switch (dtype) {
+        case VLMC_F32: rc = VLMC_IS(f32_t); break;
+        case VLMC_F16: rc = VLMC_IS(f16_t); break;
+        case VLMC_BF16: rc = VLMC_IS(bf16_t); break;
+        default: set_error("vlmc_dsnot_initial_select: unknown dtype %d", dtype); return VLMC_EINVAL;
+    }
+#undef VLMC_IS
+    if (rc != VLMC_OK) return rc;
+    VLMC_HIP_CHECK_LAUNCH("vlmc_dsnot_initial_select");
+    return VLMC_OK;
 }

@@ -21,8 +21,14 @@ Differences that are visible to a caller:
 * the standalone tower pruners accept `initial_method` (the reference reads
   `self.initial_method` in `_prune` but only the BLIP pruner sets it, :1675, so its tower
   classes cannot run on their own);
-* `initial_method="sparsegpt"` raises (the reference's branch needs a Hessian that its hook
-  never accumulates, :85-86 commented out);
+* `initial_method="sparsegpt"` runs (the reference's branch cannot: its `WrappedGPT` is built
+  without `initial_method`, :340 / ViT :1073, so `H` is never allocated).  Its contract here: the
+  Hessian of SparseGPT's `add_batch` (sparsegpt_pruner.py:68-79) over the statistics pass's calls,
+  shared by the linears fed the same tensor; `H[dead, dead] = 1`, ONE unconditional damp of
+  0.01 * mean(diag H), `U = cholesky(cholesky_inverse(cholesky(H)), upper)` (a non positive
+  definite H raises VlmcError(VLMC_ENOTPD)), initial metric fp32(w*w) / diag(U) with dead columns 0
+  (:380-402), then DSnoT's cycles as for the other initial methods; the weights are not
+  reconstructed (no OBS update), only masked;
 * `max_cycle_time >= in_features` raises instead of indexing out of range.
 
 There is no CPU fallback: without the HIP library or a GPU model the pruner raises.
@@ -45,13 +51,17 @@ class DsnotStatCollector:
     """Forward hooks on the linears of one block (dsnot_pruner.py:338-356).  Linears fed by the
     very same tensor (q/k/v, wi_0/wi_1) share one moments launch and one statistic."""
 
-    def __init__(self, subset):
+    def __init__(self, subset, hessians=False):
         from vlmc import dsnot
         self._dsnot = dsnot
         self.subset = subset
         self.calls = {n: [] for n in subset}              # per linear: one record (of one or more samples) per hook call
         self._cache = {}
         self._cur = -1
+        # initial_method="sparsegpt": per linear the SparseGPT Hessian accumulator of its input (shared like the statistics);
+        # None on the other routes (no launches, no memory)
+        self.hessians = {} if hessians else None
+        self._fed = {}                                    # input signature -> accumulator fed in this sample
         self.handles = [m.register_forward_hook(self._make_hook(n)) for n, m in subset.items()]
 
     def _make_hook(self, name):
@@ -69,10 +79,32 @@ class DsnotStatCollector:
                 hit = (x, st)                                # `x` stays referenced until the next sample (see wanda collector)
                 self._cache[key] = hit
             self.calls[name].append(hit[1])
+            if self.hessians is not None:
+                self._add_hessian(name, key, x)
         return hook
+
+    def _add_hessian(self, name, key, x):
+        """The sparsegpt_pruner's sharing rule: the first sample finds which linears receive the same tensor; each distinct input
+        is folded into its accumulator once per hook call (a stacked replay's call counts its samples: the accumulator's rule)."""
+        from vlmc import sparsegpt
+        acc = self.hessians.get(name)
+        if acc is None:
+            acc = self._fed.get(key)
+            if acc is None:
+                acc = sparsegpt.SparseGPT(self.subset[name])
+                acc.add_batch(x, None)
+                self._fed[key] = acc
+            self.hessians[name] = acc
+        elif self._fed.get(key) is not acc:
+            if key in self._fed:
+                raise RuntimeError(f"{name}: the linears sharing an input changed between calibration samples")
+            acc.add_batch(x, None)
+            self._fed[key] = acc
+        acc._keep_alive = x                                   # the signature holds only while `x` lives
 
     def next_sample(self, j=None):
         self._cache.clear()
+        self._fed.clear()
         self._cur = self._cur + 1 if j is None else j
 
     def close(self):
@@ -80,6 +112,7 @@ class DsnotStatCollector:
             h.remove()
         self.handles = []
         self._cache.clear()
+        self._fed.clear()
 
     def finalize(self):
         """{name: DsnotInputStat}; linears whose hooks saw identical tensors share the object."""
@@ -96,7 +129,29 @@ class DsnotStatCollector:
                 order.append(st)
             out[name] = st
         self._dsnot.gather_stats(order)
+        if self.hessians is not None:
+            self._divisors(out)
         return out
+
+    def _divisors(self, stats):
+        """Sample-sharded runs exchange the Hessians (the sample-weighted mean, as the SparseGPT pruner); then every distinct
+        input's divisor goes onto its statistic and the H buffers are freed."""
+        from lavis.compression.pruners.sparsegpt_pruner import _allreduce_hessians
+        from vlmc.shard import require_real_exchange
+        unique = list({id(a): a for a in self.hessians.values()}.values())
+        require_real_exchange("blipt5_dsnot_pruner (initial_method='sparsegpt')")
+        _allreduce_hessians(unique)
+        acc_of_stat = {}
+        for name, acc in self.hessians.items():
+            if acc_of_stat.setdefault(id(stats[name]), acc) is not acc:
+                raise RuntimeError(f"{name}: linears that share DSnoT statistics must share one Hessian")
+        divs = self._dsnot.sparsegpt_divisors([acc.H for acc in unique])
+        by_acc = {id(acc): d for acc, d in zip(unique, divs)}
+        for name, acc in self.hessians.items():
+            stats[name].divisor = by_acc[id(acc)]
+        for acc in unique:
+            acc.free()
+        self.hessians = {}
 
 
 class _DsnotBlockMixin:
@@ -105,7 +160,7 @@ class _DsnotBlockMixin:
     def _dsnot_block(self, i, subset, run_pass, n_inps, batch0, *, module_to_process, model_prefix, sparsity_ratio,
                      lora_model):
         from vlmc import dsnot
-        col = DsnotStatCollector(subset)
+        col = DsnotStatCollector(subset, hessians=self.initial_method == "sparsegpt")
         try:
             run_pass(col.next_sample, outputs=False)
         finally:

@@ -15,6 +15,7 @@ VLMC_OK, VLMC_EINVAL, VLMC_EHIP, VLMC_EWORKSPACE, VLMC_ENOTPD = 0, -1, -2, -3, -
 F32, F16, BF16 = 0, 1, 2
 SEL_ROW, SEL_MATRIX, SEL_NM = 0, 1, 2
 SCORE_W, SCORE_S, SCORE_ABSW_S = 0, 1, 2
+DSNOT_INIT_MAGNITUDE, DSNOT_INIT_WANDA, DSNOT_INIT_SPARSEGPT = 0, 1, 2
 
 _c = ctypes
 _p, _i, _i64, _sz = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_size_t
@@ -70,6 +71,9 @@ SIGNATURES = {
     "vlmc_dsnot_stats_update": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _i64, _p, _p]),
     "vlmc_dsnot_refine": (_i, [_p, _i, _i64, _i64, _i64, _p, _p, _p, _p, _i, _i, _i, _i, _c.c_float, _c.c_float, _i, _p, _p, _p]),
     "vlmc_dsnot_apply": (_i, [_p, _i, _i64, _i64, _i64, _p, _p, _p, _i, _i, _i, _p]),
+    "vlmc_dsnot_initial_select": (_i, [_p, _i, _i64, _i64, _i64, _p, _i, _i, _i64, _i, _i, _p, _p]),
+    "vlmc_dsnot_refine_kind": (_i, [_p, _i, _i64, _i64, _i64, _p, _p, _p, _p, _i, _p, _i, _i, _i, _c.c_float, _c.c_float, _i, _p, _p, _p]),
+    "vlmc_dsnot_divisor": (_i, [_p, _i64, _i64, _p, _p, _p]),
     "vlmc_reorder_indices": (_i, [_p, _i, _i64, _i64, _i64, _p, _i64, _p]),
     "vlmc_pack_24": (_i, [_p, _i, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p]),
     "vlmc_unpack_24": (_i, [_p, _p, _i, _i64, _i64, _p, _i64, _p, _i64, _p, _p]),

@@ -3,7 +3,8 @@
 Mirrors the DSnoT `WrappedGPT` state (dsnot_pruner.py:53-105) and the per-linear body of
 `_prune` (:378-751).  Per linear:
     initial mask   vlmc_wanda_select (row rule with k = round(in*ratio), or n:m; magnitude init =
-                   the same kernel with a unit scale) -- no weights touched
+                   the same kernel with a unit scale) -- no weights touched; initial_method="sparsegpt":
+                   vlmc_dsnot_initial_select with the saliency w^2 / diag(U) (`sparsegpt_divisors`)
     refinement     vlmc_dsnot_refine: every row's whole cycle loop in ONE launch (the reference
                    issues ~20 small kernels per cycle for up to 100 cycles after three full-row sorts)
     replay/apply   vlmc_dsnot_apply with C = min(max_cycle, max over rows of the stop cycle)
@@ -66,6 +67,7 @@ class DsnotInputStat:
         self.blocks = []
         self.scaler_row = self.sum_row = self.var_row = self.sqrt_row = None
         self.nsamples = self.ntokens = 0
+        self.divisor = None          # initial_method="sparsegpt": [in] fp32 diag(U), +inf for dead columns (sparsegpt_divisors)
 
     def add_call(self, x: torch.Tensor, sample=None):
         b = x.shape[0] if x.dim() == 3 else 1
@@ -135,6 +137,67 @@ def gather_stats(stats):
     return stats
 
 
+def _factor_budget(sizes, dev):
+    """Workgroups each persistent factorization launched together may take: the CUs shared in proportion to the tile counts,
+    at least 8 each (the rule of sparsegpt.factorize_many)."""
+    from .sparsegpt import _CHOL_NB
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    tot = sum((n // _CHOL_NB) ** 2 for n in sizes) or 1
+    return {n: max(8, min((n // _CHOL_NB) ** 2, (cus * (n // _CHOL_NB) ** 2) // tot)) for n in set(sizes)}
+
+
+@torch.no_grad()
+def sparsegpt_divisors(hessians, percdamp=0.01):
+    """The divisor of DSnoT's SparseGPT initial metric for each Hessian of a block (dsnot_pruner.py:380-402): `dead = diag(H) == 0`,
+    `H[dead, dead] = 1`, ONE unconditional `H += percdamp * mean(diag H) I`, `U = cholesky(cholesky_inverse(cholesky(H)), upper)`
+    from one factorization (sparsegpt.inverse_upper_factor); div = diag(U), +inf for a dead column (vlmc_dsnot_divisor).
+    Consumes the Hessians.  The factorizations run side by side on the sweep streams; ONE host read checks them all, and a
+    Hessian that is not positive definite raises VlmcError(VLMC_ENOTPD) as the reference's `torch.linalg.cholesky` would -- no
+    retry with more damping (that is the SparseGPT pruner's rule, not this branch's)."""
+    from . import sparsegpt
+    if not hessians:
+        return []
+    _need_gpu(*hessians)
+    dev = hessians[0].device
+    lib = _lib.load()
+    main = torch.cuda.current_stream(dev)
+    streams = sparsegpt.sweep_streams(dev) if len(hessians) > 1 else []
+    budget = _factor_budget([H.shape[0] for H in hessians], dev) if all(sparsegpt.persistent_factor_usable(H.shape[0])
+                                                                          for H in hessians) else {}
+    slots, out, bad = {}, [None] * len(hessians), []
+    order = sorted(range(len(hessians)), key=lambda i: -hessians[i].shape[0])        # the largest chains first
+    for j, i in enumerate(order):
+        H = hessians[i]
+        n = H.shape[0]
+        dead = torch.diag(H) == 0
+        H.diagonal().masked_fill_(dead, 1.0)                                         # H[dead, dead] = 1 (:384)
+        H.diagonal().add_(percdamp * torch.mean(torch.diag(H)))                      # (:388-392) once, unconditionally
+        slot = slots.get(n, 0)
+        slots[n] = slot + 1
+        st = streams[j % len(streams)] if streams else main
+        st.wait_stream(main)
+        with torch.cuda.stream(st):
+            U, info = sparsegpt.inverse_upper_factor(H, slot=slot, max_workgroups=budget.get(n))
+            div = torch.empty(n, dtype=torch.float32, device=dev)
+            _lib.check(lib.vlmc_dsnot_divisor(U.data_ptr(), n, U.stride(0), dead.data_ptr(), div.data_ptr(), _stream()))
+            flag = (info != 0).any() | torch.isnan(U).any()
+        if st is not main:
+            for t in (div, flag):
+                t.record_stream(main)
+            dead.record_stream(st)
+            U.record_stream(st)
+        out[i] = div
+        bad.append((i, flag))
+    for st in streams:
+        main.wait_stream(st)
+    flags = torch.stack([f for _, f in bad]).cpu().tolist()                          # the ONE host read
+    for (i, _), f in zip(bad, flags):
+        if f:
+            raise _lib.VlmcError(_lib.VLMC_ENOTPD, f"DSnoT sparsegpt init: H + damp I is not positive definite (n = "
+                                 f"{hessians[i].shape[0]}); the reference's torch.linalg.cholesky raises here (dsnot_pruner.py:397)")
+    return out
+
+
 @torch.no_grad()
 def reorder_indices(input_tensor: torch.Tensor) -> torch.Tensor:
     """`return_reorder_indice(input_tensor)` (dsnot_pruner.py:1881-1925) on the GPU: int64 [rows, cols]; per row the indices of the
@@ -160,21 +223,35 @@ def prune_linear(weight: torch.Tensor, stat: DsnotInputStat, ratio, *, prune_n=0
                  without_DSnoT=False, max_cycle_time=100, update_threshold=0.1, pow_of_var_regrowing=1.0,
                  without_same_sign=True, apply_zero=True):
     """Per-linear body of the DSnoT `_prune` loops.  Returns the keep mask (torch.bool, True = keep),
-    or None when ratio == 0 in the unstructured branch (the reference skips the linear, :560-561)."""
+    or None when ratio == 0 in the unstructured branch (the reference skips the linear, :560-561).
+    initial_method="sparsegpt" reads the divisor `stat.divisor` (sparsegpt_divisors); the weights get no OBS update."""
     _need_gpu(weight)
-    if initial_method not in ("wanda", "magnitude"):
-        raise ValueError("initial_method must be 'wanda' or 'magnitude' (the reference's 'sparsegpt' branch cannot run: "
-                         "its Hessian is never allocated, dsnot_pruner.py:340,386)")
+    if initial_method not in ("wanda", "magnitude", "sparsegpt"):
+        raise ValueError(f"initial_method must be 'wanda', 'magnitude' or 'sparsegpt' (got {initial_method!r})")
     out_f, in_f = weight.shape
-    init_scale = stat.sqrt_row if initial_method == "wanda" else torch.ones_like(stat.sqrt_row)
     max_cycle = int(max_cycle_time)
-    if prune_n != 0:
-        keep, _ = ops.wanda_select(weight, init_scale, "nm", n=prune_n, m=prune_m, apply_zero=False)
-    else:
-        if ratio == 0.:
-            return None
-        keep, _ = ops.wanda_select(weight, init_scale, "row", k=round(in_f * ratio), apply_zero=False)     # :562 round()
     lib = _lib.load()
+    if initial_method == "sparsegpt":
+        div = stat.divisor
+        if div is None:
+            raise ValueError("initial_method='sparsegpt' needs the statistic's divisor (dsnot.sparsegpt_divisors)")
+        _need_gpu(div)
+        if prune_n == 0 and ratio == 0.:
+            return None
+        keep = torch.empty((out_f, in_f), dtype=torch.bool, device=weight.device)
+        _lib.check(lib.vlmc_dsnot_initial_select(
+            weight.data_ptr(), _dtype_code(weight), out_f, in_f, weight.stride(0), div.data_ptr(), _lib.DSNOT_INIT_SPARSEGPT,
+            _lib.SEL_NM if prune_n != 0 else _lib.SEL_ROW, 0 if prune_n != 0 else round(in_f * ratio), int(prune_n), int(prune_m),
+            keep.data_ptr(), _stream()))
+    else:
+        div = None
+        init_scale = stat.sqrt_row if initial_method == "wanda" else torch.ones_like(stat.sqrt_row)
+        if prune_n != 0:
+            keep, _ = ops.wanda_select(weight, init_scale, "nm", n=prune_n, m=prune_m, apply_zero=False)
+        else:
+            if ratio == 0.:
+                return None
+            keep, _ = ops.wanda_select(weight, init_scale, "row", k=round(in_f * ratio), apply_zero=False)     # :562 round()
     ncyc = torch.zeros(1, dtype=torch.int32, device=weight.device)
     events = torch.empty((out_f, max(max_cycle, 1)), dtype=torch.int32, device=weight.device)
     if not (prune_n == 0 and without_DSnoT):
@@ -182,11 +259,18 @@ def prune_linear(weight: torch.Tensor, stat: DsnotInputStat, ratio, *, prune_n=0
             raise RuntimeError(f"DSnoT needs in_features ({in_f}) > max_cycle_time ({max_cycle}); the reference's pointers "
                                "run out of range in that case (SURVEY.md Appendix B.1)")
         stop = torch.empty(out_f, dtype=torch.int32, device=weight.device)
-        _lib.check(lib.vlmc_dsnot_refine(
-            weight.data_ptr(), _dtype_code(weight), out_f, in_f, weight.stride(0), keep.data_ptr(), stat.sqrt_row.data_ptr(),
-            stat.sum_row.data_ptr(), stat.var_row.data_ptr(), int(initial_method == "wanda"), int(prune_n), int(prune_m),
-            max_cycle, float(update_threshold), float(pow_of_var_regrowing or 0.0), int(bool(without_same_sign)),
-            events.data_ptr(), stop.data_ptr(), _stream()))
+        if div is None:
+            _lib.check(lib.vlmc_dsnot_refine(
+                weight.data_ptr(), _dtype_code(weight), out_f, in_f, weight.stride(0), keep.data_ptr(), stat.sqrt_row.data_ptr(),
+                stat.sum_row.data_ptr(), stat.var_row.data_ptr(), int(initial_method == "wanda"), int(prune_n), int(prune_m),
+                max_cycle, float(update_threshold), float(pow_of_var_regrowing or 0.0), int(bool(without_same_sign)),
+                events.data_ptr(), stop.data_ptr(), _stream()))
+        else:
+            _lib.check(lib.vlmc_dsnot_refine_kind(
+                weight.data_ptr(), _dtype_code(weight), out_f, in_f, weight.stride(0), keep.data_ptr(), stat.sqrt_row.data_ptr(),
+                stat.sum_row.data_ptr(), stat.var_row.data_ptr(), _lib.DSNOT_INIT_SPARSEGPT, div.data_ptr(), int(prune_n),
+                int(prune_m), max_cycle, float(update_threshold), float(pow_of_var_regrowing or 0.0), int(bool(without_same_sign)),
+                events.data_ptr(), stop.data_ptr(), _stream()))
         ncyc = stop.max().clamp(max=max_cycle).to(torch.int32).reshape(1)
     _lib.check(lib.vlmc_dsnot_apply(weight.data_ptr(), _dtype_code(weight), out_f, in_f, weight.stride(0), keep.data_ptr(),
                                     events.data_ptr(), ncyc.data_ptr(), max(max_cycle, 1), int(prune_n != 0),
