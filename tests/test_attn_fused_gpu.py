@@ -67,10 +67,9 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
-def test_fused_chain_has_the_bits_of_the_unfused_sequence(case):
+def _case_inputs(case):
+    """q, k, v, addends and the fp32 multiplier of a row of CASES"""
     name, dtype, B, H, Tq, Tk, d, mul, add_shapes, f32 = case
-    ops = _ops()
     g = _gen(len(name))
     q, k, v = _heads(B, Tq, H, d, dtype, g, 0.6), _heads(B, Tk, H, d, dtype, g, 0.6), _heads(B, Tk, H, d, dtype, g)
     adds = []
@@ -81,20 +80,33 @@ def test_fused_chain_has_the_bits_of_the_unfused_sequence(case):
         adds.append(t)
     import numpy as np
     m32 = None if mul is None else float(np.float32(mul))
-    got = ops.attn_fused(q, k, v, m32, adds)
-    want = _unfused(q, k, v, mul=m32, adds=adds, f32_softmax=f32)
-    assert got.shape == want.shape == (B, H, Tq, d)
-    assert got.transpose(1, 2).is_contiguous()                             # [B, Tq, H, d]: the model's reshape is a view
-    assert torch.equal(_bits(got), _bits(want)), f"{name}: {int((_bits(got) != _bits(want)).sum())} of {got.numel()} entries differ"
-    # .. and both are what the chain is in exact arithmetic, up to the roundings it prescribes
+    return q, k, v, adds, m32
+
+
+def _check_against_fp64(got, q, k, v, adds, m32):
+    """the chain in exact arithmetic, up to the roundings it prescribes"""
     s = q.double() @ k.double().transpose(-1, -2)
     if m32 is not None:
         s = s * m32
     for t in adds:
         s = s + t.double()
     ref = torch.softmax(s, -1) @ v.double()
-    tol = 3e-2 if dtype == torch.bfloat16 else 4e-3
+    tol = 3e-2 if q.dtype == torch.bfloat16 else 4e-3
     assert (got.double() - ref).abs().max() <= tol * max(1.0, float(ref.abs().max()))
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_fused_chain_has_the_bits_of_the_unfused_sequence(case):
+    name, dtype, B, H, Tq, Tk, d, mul, add_shapes, f32 = case
+    ops = _ops()
+    q, k, v, adds, m32 = _case_inputs(case)
+    got = ops.attn_fused(q, k, v, m32, adds)
+    want = _unfused(q, k, v, mul=m32, adds=adds, f32_softmax=f32)
+    assert got.shape == want.shape == (B, H, Tq, d)
+    assert got.transpose(1, 2).is_contiguous()                             # [B, Tq, H, d]: the model's reshape is a view
+    assert torch.equal(_bits(got), _bits(want)), f"{name}: {int((_bits(got) != _bits(want)).sum())} of {got.numel()} entries differ"
+    # .. and both are what the chain is in exact arithmetic, up to the roundings it prescribes
+    _check_against_fp64(got, q, k, v, adds, m32)
 
 
 def test_permuted_position_bias_is_read_through_its_strides():
@@ -154,16 +166,15 @@ def test_a_sample_has_the_same_bits_alone_in_a_group_and_padded():
     assert torch.equal(_bits(grouped), _bits(_unfused(pad(qs), pad(ks), pad(vs), adds=[full], f32_softmax=True)))
 
 
-@pytest.mark.parametrize("dtype,H,d,lens_q,lens_k,nadd", [
+LENS_CASES = [
     (torch.bfloat16, 32, 64, [40, 160, 48, 96, 33], None, 1),                 # T5 encoder self-attention, ragged (keys = queries)
     (torch.bfloat16, 32, 64, [4, 16, 8, 16, 1], [40, 160, 48, 96, 33], 2),    # T5 cross-attention: ragged answers over ragged prompts
     (torch.float16, 12, 64, [40, 64, 33], None, 1),                           # Q-Former self-attention with text
     (torch.float16, 16, 88, [257, 100, 17], None, 1),                         # head_dim 88, three K-steps along d, the 8-wave kernel
-])
-def test_lengths_skip_the_padding_and_keep_the_live_bits(dtype, H, d, lens_q, lens_k, nadd):
-    """vlmc_attn_fwd_lens: with per-sample key / query counts the masked keys are neither staged nor multiplied and the padding
-    queries come out as zeros; every live row has the bits of the launch without lengths (and therefore of the sample alone)."""
-    ops = _ops()
+]
+
+
+def _lens_inputs(dtype, H, d, lens_q, lens_k, nadd):
     g = _gen(17 + d)
     lens_k = lens_q if lens_k is None else lens_k
     B, Tq, Tk = len(lens_q), max(lens_q), max(lens_k)
@@ -181,6 +192,16 @@ def test_lengths_skip_the_padding_and_keep_the_live_bits(dtype, H, d, lens_q, le
     adds = [bias + mask] if nadd == 1 else [bias, mask]
     ql = torch.tensor(lens_q, dtype=torch.int32, device=DEV)
     kl = torch.tensor(lens_k, dtype=torch.int32, device=DEV)
+    return q, k, v, adds, ql, kl
+
+
+@pytest.mark.parametrize("dtype,H,d,lens_q,lens_k,nadd", LENS_CASES)
+def test_lengths_skip_the_padding_and_keep_the_live_bits(dtype, H, d, lens_q, lens_k, nadd):
+    """vlmc_attn_fwd_lens: with per-sample key / query counts the masked keys are neither staged nor multiplied and the padding
+    queries come out as zeros; every live row has the bits of the launch without lengths (and therefore of the sample alone)."""
+    ops = _ops()
+    q, k, v, adds, ql, kl = _lens_inputs(dtype, H, d, lens_q, lens_k, nadd)
+    B = len(lens_q)
     full = ops.attn_fused(q, k, v, None, adds)
     for kw in (dict(q_len=ql, k_len=kl), dict(k_len=kl), dict(q_len=ql)):
         cut = ops.attn_fused(q, k, v, None, adds, **kw)
@@ -211,6 +232,84 @@ def test_operands_are_read_in_place_through_their_strides():
     k2 = base[1:1 + B * H * N * d].view(B, H, N, d)
     v2 = base[3:3 + B * H * N * d].view(B, H, N, d)
     assert torch.equal(_bits(ops.attn_fused(q, k2, v2)), _bits(ops.attn_fused(q, k2.clone(), v2.clone())))
+
+
+# ---- K / V staging (csrc/attn_fused.hip: LDS-DMA where K and V rows are 16-byte aligned, else through registers; VLMC_ATTN_DMA=0
+# forces the register route everywhere): both routes must give the same bits.
+MISALIGNED_LENS = [40, 17, 64, 5]
+
+
+def _misaligned_inputs():
+    """bf16, head_dim 64, two addends, ragged lengths: K and V are [B, H, T, d] views of [B, T, H d] buffers that start one element
+    (2 bytes) in, so that no row of theirs is 16-byte aligned; the aligned copies keep the layout"""
+    dtype, H, d = torch.bfloat16, 8, 64
+    q, _, _, adds, ql, kl = _lens_inputs(dtype, H, d, MISALIGNED_LENS, None, 2)
+    B, T = len(MISALIGNED_LENS), max(MISALIGNED_LENS)
+    g = _gen(99)
+    kv = []
+    for scale in (0.6, 1.0):
+        buf = (torch.randn(B * T * H * d + 1, generator=g, device=DEV) * scale).to(dtype)
+        t = buf[1:].view(B, T, H, d).transpose(1, 2)
+        for i, n in enumerate(MISALIGNED_LENS):
+            t[i, :, n:] = 0
+        kv.append(t)
+    return q, kv[0], kv[1], adds, ql, kl
+
+
+def attn_staging_outputs():
+    """Every row of CASES and of LENS_CASES, and the misaligned bf16 case with its aligned copies (run once per VLMC_ATTN_DMA value in
+    a child process: tests/variant_runs.py)."""
+    ops = _ops()
+    out = {"cases": [], "lens": [], "misaligned": []}
+    for case in CASES:
+        q, k, v, adds, m32 = _case_inputs(case)
+        out["cases"].append(ops.attn_fused(q, k, v, m32, adds).cpu())
+    for row in LENS_CASES:
+        q, k, v, adds, ql, kl = _lens_inputs(*row)
+        out["lens"].append([ops.attn_fused(q, k, v, None, adds, **kw).cpu()
+                            for kw in ({}, dict(q_len=ql, k_len=kl), dict(k_len=kl), dict(q_len=ql))])
+    q, k, v, adds, ql, kl = _misaligned_inputs()
+    assert k.data_ptr() % 16 != 0 and v.data_ptr() % 16 != 0
+    for kk, vv in ((k, v), (k.clone(), v.clone())):
+        out["misaligned"] += [ops.attn_fused(q, kk, vv, None, adds, q_len=ql, k_len=kl).cpu(), ops.attn_fused(q, kk, vv, None, adds).cpu()]
+    return out
+
+
+@pytest.fixture(scope="module")
+def attn_staging(tmp_path_factory):
+    import variant_runs
+    return variant_runs.run_variants(tmp_path_factory.mktemp("attn_staging"), "test_attn_fused_gpu", "attn_staging_outputs",
+                                     {"default": {}, "registers": {"VLMC_ATTN_DMA": "0"}})
+
+
+def test_lds_dma_and_register_staging_give_the_same_bits(attn_staging):
+    """VLMC_ATTN_DMA = 1 / 0: every row of CASES (bf16 and fp16, head_dim 32 / 64 / 88 / 96 / 128, no, one and two addends, up to 512
+    keys), the length-cut launches, and misaligned K / V against their aligned copies."""
+    import variant_runs
+    variant_runs.assert_variants_agree(attn_staging)
+    for label, out in attn_staging.items():
+        mis = out["misaligned"]
+        assert torch.equal(_bits(mis[0]), _bits(mis[2])) and torch.equal(_bits(mis[1]), _bits(mis[3])), label
+        for i, n in enumerate(MISALIGNED_LENS):
+            assert torch.equal(_bits(mis[0][i, :, :n]), _bits(mis[1][i, :, :n])), (label, i)
+            assert bool((_bits(mis[0][i, :, n:]) == 0).all()), (label, i)
+        for row, (full, *cuts) in zip(LENS_CASES, out["lens"]):
+            for cut in cuts:
+                for i, n in enumerate(row[3]):
+                    assert torch.equal(_bits(cut[i, :, :n]), _bits(full[i, :, :n])), (label, row[:3], i)
+
+
+def test_register_staging_against_fp64(attn_staging):
+    """The register route's outputs against the chain in float64 (the bound of test_fused_chain_has_the_bits_of_the_unfused_sequence)."""
+    out = attn_staging["registers"]
+    for case, got in zip(CASES, out["cases"]):
+        q, k, v, adds, m32 = _case_inputs(case)
+        _check_against_fp64(got.to(DEV), q, k, v, adds, m32)
+    q, k, v, adds, ql, kl = _misaligned_inputs()
+    got = out["misaligned"][1].to(DEV)
+    for i, n in enumerate(MISALIGNED_LENS):
+        _check_against_fp64(got[i:i + 1, :, :n], q[i:i + 1, :, :n], k[i:i + 1, :, :n], v[i:i + 1, :, :n],
+                            [t[i:i + 1, :, :n, :n] if t.shape[0] > 1 else t[..., :n, :n] for t in adds], None)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])

@@ -9,6 +9,7 @@ import torch
 
 import golden_io
 from oracle import dsnot as OD
+from test_dsnot_sgpt import sgpt_oracle  # noqa: F401  (fixture: the oracle's metrics with the sparsegpt branch)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -259,3 +260,91 @@ def test_return_reorder_indice_refuses_cpu_tensors():
     from lavis.compression.pruners.dsnot_pruner import return_reorder_indice
     with pytest.raises(RuntimeError, match="GPU only"):
         return_reorder_indice(torch.randn(2, 3))
+
+
+# ---- waves per row of the cycle kernel (csrc/dsnot.hip: simulate_dispatch takes 1 / 4 / 8 waves by the row's width; VLMC_DSNOT_NW
+# forces 1 / 2 / 4 / 8 where the row fits): every wave count gives the same masks, weights and events.  The variable is read by the
+# per-cycle kernel, the route of VLMC_DSNOT_LISTS=0 (the list kernel is the default and checked against it above).
+NW_CASES = [(torch.bfloat16, 1408), (torch.float16, 2048), (torch.bfloat16, 4096), (torch.float16, 5120)]
+NW_KINDS = [(n, m, init) for n, m in ((0, 0), (2, 4)) for init in ("wanda", "sparsegpt")]
+NW_MC, NW_THR = 100, 0.05
+
+
+def _nw_inputs(dtype, in_f):
+    from test_dsnot_sgpt_gpu import _case
+    return _case(32, in_f, dtype, seed=in_f + 3, dead=5)
+
+
+def _nw_refine_events(Wd, st, n, m, init):
+    """the initial select, then one refinement with its events and stop cycles"""
+    from vlmc import _lib, ops
+    from vlmc.ops import _dtype_code, _stream
+    lib = _lib.load()
+    out_f, in_f = Wd.shape
+    if init == "wanda":
+        keep, _ = ops.wanda_select(Wd, st.sqrt_row, "nm", n=n, m=m, apply_zero=False) if n else \
+            ops.wanda_select(Wd, st.sqrt_row, "row", k=in_f // 2, apply_zero=False)
+    else:
+        keep = torch.empty((out_f, in_f), dtype=torch.bool, device=DEV)
+        _lib.check(lib.vlmc_dsnot_initial_select(Wd.data_ptr(), _dtype_code(Wd), out_f, in_f, Wd.stride(0), st.divisor.data_ptr(),
+                                                 _lib.DSNOT_INIT_SPARSEGPT, _lib.SEL_NM if n else _lib.SEL_ROW, 0 if n else in_f // 2,
+                                                 n, m, keep.data_ptr(), _stream()))
+    events = torch.zeros((out_f, NW_MC), dtype=torch.int32, device=DEV)
+    stop = torch.zeros(out_f, dtype=torch.int32, device=DEV)
+    kind = _lib.DSNOT_INIT_WANDA if init == "wanda" else _lib.DSNOT_INIT_SPARSEGPT
+    _lib.check(lib.vlmc_dsnot_refine_kind(Wd.data_ptr(), _dtype_code(Wd), out_f, in_f, Wd.stride(0), keep.data_ptr(), st.sqrt_row.data_ptr(),
+                                          st.sum_row.data_ptr(), st.var_row.data_ptr(), kind,
+                                          st.divisor.data_ptr() if init == "sparsegpt" else None, n, m, NW_MC, NW_THR, 1.0, 1,
+                                          events.data_ptr(), stop.data_ptr(), _stream()))
+    return keep.cpu(), events.cpu(), stop.cpu()
+
+
+def dsnot_nw_outputs():
+    """keep mask, pruned weights, initial mask, events and stop cycles per (width, n:m, initial kind)  (run once per VLMC_DSNOT_NW
+    value in a child process: tests/variant_runs.py)"""
+    from types import SimpleNamespace
+    from vlmc import dsnot
+    out = []
+    for dtype, in_f in NW_CASES:
+        W, scaler, sq, sum_row, var_row, div = _nw_inputs(dtype, in_f)
+        st = SimpleNamespace(sqrt_row=sq.to(DEV), sum_row=sum_row.to(DEV), var_row=var_row.to(DEV), divisor=div.to(DEV))
+        for n, m, init in NW_KINDS:
+            Wd = W.to(DEV).contiguous()
+            keep = dsnot.prune_linear(Wd, st, 0.5, prune_n=n, prune_m=m, initial_method=init, max_cycle_time=NW_MC, update_threshold=NW_THR)
+            out.append([keep.cpu(), Wd.cpu(), *_nw_refine_events(W.to(DEV).contiguous(), st, n, m, init)])
+    return out
+
+
+@pytest.fixture(scope="module")
+def dsnot_nw(tmp_path_factory):
+    import variant_runs
+    cycles = {"VLMC_DSNOT_LISTS": "0"}
+    return variant_runs.run_variants(tmp_path_factory.mktemp("dsnot_nw"), "test_dsnot_gpu", "dsnot_nw_outputs",
+                                     {"default": cycles, **{str(w): dict(cycles, VLMC_DSNOT_NW=str(w)) for w in (1, 2, 4, 8)}})
+
+
+def test_cycle_kernel_wave_counts_give_the_same_bits(dsnot_nw):
+    """VLMC_DSNOT_NW = 1 / 2 / 4 / 8 (a count too small for the row is ignored: 1 at 4096 and 5120, 2 at 5120) and the width rule,
+    at 1408 / 2048 / 4096 / 5120 columns, unstructured and 2:4, Wanda and SparseGPT initial masks; and the list kernel of the default
+    route (this process) has the same masks, weights and events."""
+    import variant_runs
+    variant_runs.assert_variants_agree(dsnot_nw)
+    lists = dsnot_nw_outputs()
+    variant_runs.assert_variants_agree({"default": dsnot_nw["default"], "lists": lists})
+
+
+def test_cycle_kernel_wave_counts_against_the_oracle(dsnot_nw, sgpt_oracle):
+    """the masks and pruned weights of every wave count against the CPU oracle (with the sparsegpt metric: tests/test_dsnot_sgpt.py)"""
+    from types import SimpleNamespace
+    k = 0
+    for dtype, in_f in NW_CASES:
+        W, scaler, sq, sum_row, var_row, div = _nw_inputs(dtype, in_f)
+        ost = SimpleNamespace(scaler_row=scaler, sum_metric_row=sum_row, var=var_row.reshape(-1, 1), divisor=div)
+        for n, m, init in NW_KINDS:
+            kw = dict(initial_method=init, max_cycle_time=NW_MC, update_threshold=NW_THR)
+            want = ~(OD.prune_nm(W, ost, n, m, **kw) if n else OD.prune_unstructured(W, ost, 0.5, **kw))
+            for label, res in dsnot_nw.items():
+                keep, Wn = res[k][:2]
+                assert torch.equal(keep, want), (label, in_f, n, m, init, int((keep != want).sum()))
+                assert torch.equal(Wn, W.masked_fill(~want, 0)), (label, in_f, n, m, init)
+            k += 1

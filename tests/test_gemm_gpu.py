@@ -593,3 +593,168 @@ def test_gelu_fp32_is_torchs_body_arithmetic_everywhere():
     assert torch.allclose(y[:4096 * 3], ref, rtol=2e-6, atol=1e-7)
     assert torch.equal(ops.gelu(x[100:]), y[100:])                                          # position in the tensor does not matter
     assert torch.allclose(ops.gelu(x, "tanh"), torch.nn.functional.gelu(x, approximate="tanh"), rtol=1e-5, atol=1e-6)
+
+
+# ---- the fp32 GEMM's tile sizes (csrc/gemm_f32.hip: launch_f32 picks 128 / 64 / 32 by the launch's size; VLMC_F32_TILE forces one) --
+# Every tile must give an output element the same bits: a calibration sample runs alone on the 32 tile while a stack of samples
+# runs on the 64 or 128 tile, and the stacked capture and the row-mapped linears rely on both being the sample's own forward.
+F32_EDGES = [1, 31, 33, 64, 65, 127, 129, 257]                              # M and N across every tile's edge
+F32_KS = [1, 3, 4, 5, 31, 32, 33, 63, 65, 127, 128, 129, 768, 1408, 3072]   # K across every chunk's (128 / 64 / 32) edge
+F32_RAGGED = [([40, 104, 7, 160, 33, 99, 128, 61], 160, 768, 768),         # 648 padding rows: several zero blocks for every tile
+              ([40, 104, 7, 160, 33, 99, 128, 61] * 6, 160, 768, 3072),    # the size rule's 128 tile
+              ([5, 1, 9, 3, 70, 2] * 30, 70, 65, 129)]                     # odd K and N, 6336 padding rows
+F32_GATHER = [([40, 104, 39, 160, 33, 99, 128, 61] * 4, 160, 32, 128, 768, 3072), ([5, 1, 9, 3] * 40, 9, 2, 7, 33, 65)]
+F32_ATTN = [(3, 12, 45, 45, 64), (2, 4, 129, 65, 33), (1, 3, 257, 33, 127), (2, 12, 257, 257, 64), (16, 12, 160, 160, 64)]
+F32_PRUNE = [(4096, 3072, 768), (20480, 768, 768)]                          # the rule's 128 and 64 tiles on a 256-CU device
+
+
+def _f32_cases():
+    """(M, N, K, bias, layout of X): every M and N edge meets every K; the layouts take both load branches of `fetch`."""
+    cases = []
+    for i, K in enumerate(F32_KS):
+        for j, M in enumerate(F32_EDGES):
+            cases.append((M, F32_EDGES[(i + j + 3) % len(F32_EDGES)], K, (i + j) % 2 == 0, ("dense", "stride", "offset")[(i + 2 * j) % 3]))
+    return cases
+
+
+def _f32_linear_inputs(M, N, K, bias, layout, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(M, K, generator=g) * 0.5 + 0.1
+    w = torch.randn(N, K, generator=g) * 0.05
+    b = torch.randn(N, generator=g) * 0.1 if bias else None
+    if layout == "stride":                                  # rows of X (and W) at a pitch that is no multiple of 4 floats
+        pad = 1 if (K + 1) % 4 else 2
+        x = torch.cat([x, torch.full((M, pad), float("nan"))], 1).to(DEV)[:, :K]
+        w = torch.cat([w, torch.full((N, pad), float("nan"))], 1).to(DEV)[:, :K]
+    elif layout == "offset":                                # X starts 4 bytes into its buffer: no 16-byte loads
+        x = torch.cat([torch.full((1,), float("nan")), x.reshape(-1)]).to(DEV)[1:].view(M, K)
+    x, w = x.to(DEV), w.to(DEV)
+    return x, w, b.to(DEV) if b is not None else None
+
+
+def _f32_ragged_inputs(lengths, tpad, K, N):
+    x, rowmap, n_real = _ragged_case(torch.float32, lengths, tpad, K, seed=len(lengths) * 7 + K)
+    g = torch.Generator(device=DEV).manual_seed(N + K)
+    return x, rowmap, n_real, torch.randn(N, K, generator=g, device=DEV) * 0.05, torch.randn(N, generator=g, device=DEV) * 0.1
+
+
+def _f32_gather_inputs(lengths, P, a, L, K, N):
+    import numpy as np
+    n = len(lengths)
+    g = torch.Generator(device=DEV).manual_seed(P + a + L + K)
+    base = torch.randn(n, P, K, generator=g, device=DEV) * 0.5 + 0.1
+    for j, t in enumerate(lengths):
+        base[j, t:] = float("nan")
+    w = torch.randn(N, K, generator=g, device=DEV) * 0.05
+    b = torch.randn(N, generator=g, device=DEV) * 0.1
+    ln = np.clip(np.asarray(lengths) - a, 0, L)
+    tok = np.arange(L)[None, :]
+    real = tok < ln[:, None]
+    xi, yi = np.arange(n)[:, None] * P + tok, np.arange(n)[:, None] * L + tok
+    x_rows = torch.from_numpy(xi[real].astype(np.int32)).to(DEV)
+    y_rows = torch.from_numpy(np.concatenate([yi[real], yi[~real]]).astype(np.int32)).to(DEV)
+    return base, w, b, x_rows, y_rows, int(real.sum()), ln
+
+
+def _f32_attn_inputs(B, H, Tq, Tk, d):
+    g = torch.Generator(device=DEV).manual_seed(B * 1000 + Tq + Tk + d)
+    q = torch.randn(B, Tq, H, d, generator=g, device=DEV).permute(0, 2, 1, 3)
+    k = torch.randn(B, Tk, H, d, generator=g, device=DEV).permute(0, 2, 1, 3)
+    v = torch.randn(B, Tk, H, d, generator=g, device=DEV).permute(0, 2, 1, 3)
+    p = torch.softmax(torch.randn(B, H, Tq, Tk, generator=g, device=DEV), -1)          # (like softmax(q k^T / 8) of the Q-Former)
+    return q, k, v, p
+
+
+def _f32_prune_inputs(M, N, K):
+    g = torch.Generator(device=DEV).manual_seed(M + N + K)
+    return (torch.randn(M, K, generator=g, device=DEV) * 0.5 + 0.1, torch.randn(N, K, generator=g, device=DEV) * 0.05,
+            torch.randn(N, generator=g, device=DEV) * 0.1)
+
+
+def f32_tile_outputs():
+    """Every fp32 entry point at the tile-edge shapes (run once per VLMC_F32_TILE value, in a child process: tests/variant_runs.py)."""
+    from vlmc import ops
+    out = {"linear": [], "rows": [], "gather": [], "qk": [], "pv": [], "prune": []}
+    for i, case in enumerate(_f32_cases()):
+        x, w, b = _f32_linear_inputs(*case, seed=i)
+        out["linear"].append(ops.linear_fwd(x, w, b).cpu())
+    for lengths, tpad, K, N in F32_RAGGED:
+        x, rowmap, n_real, w, b = _f32_ragged_inputs(lengths, tpad, K, N)
+        y = ops.linear_fwd_rows(x, [w, w], [b, None], rowmap, n_real)
+        out["rows"].append([t.cpu() for t in y])
+    for lengths, P, a, L, K, N in F32_GATHER:
+        base, w, b, x_rows, y_rows, n_real, _ = _f32_gather_inputs(lengths, P, a, L, K, N)
+        out["gather"].append(ops.linear_fwd_gather(base[:, a:a + L], w, b, x_rows, y_rows, n_real, len(lengths) * L, K).cpu())
+    for shape in F32_ATTN:
+        q, k, v, p = _f32_attn_inputs(*shape)
+        out["qk"].append(ops.attn_matmul(q, k.transpose(-1, -2)).cpu())        # B k-contiguous
+        out["pv"].append(ops.attn_matmul(p, v).cpu())                          # B n-contiguous
+    for shape in F32_PRUNE:
+        out["prune"].append(ops.linear_fwd(*_f32_prune_inputs(*shape)).cpu())
+    return out
+
+
+@pytest.fixture(scope="module")
+def f32_tiles(tmp_path_factory):
+    import variant_runs
+    return variant_runs.run_variants(tmp_path_factory.mktemp("f32_tiles"), "test_gemm_gpu", "f32_tile_outputs",
+                                     {"default": {}, "128": {"VLMC_F32_TILE": "128"}, "64": {"VLMC_F32_TILE": "64"},
+                                      "32": {"VLMC_F32_TILE": "32"}})
+
+
+def test_f32_tiles_give_the_same_bits(f32_tiles):
+    """VLMC_F32_TILE = 128 / 64 / 32 and the size rule: linear_fwd, linear_fwd_rows, linear_fwd_gather and both attn_matmul layouts
+    at every tile and K-chunk edge, strided and misaligned X, with and without bias, and the prune-size shapes."""
+    import variant_runs
+    variant_runs.assert_variants_agree(f32_tiles)
+
+
+def _f32_close(y, ref, scale):
+    """the bound of test_linear_fwd_fp32_matches_fp64_and_is_batch_invariant"""
+    return bool(((y.double() - ref).abs() <= 1e-6 * scale + 1e-30).all())
+
+
+@pytest.mark.parametrize("tile", ["default", "128", "64", "32"])
+def test_f32_tiles_against_fp64(f32_tiles, tile):
+    out = f32_tiles[tile]
+    for i, case in enumerate(_f32_cases()):
+        x, w, b = _f32_linear_inputs(*case, seed=i)
+        ref = _ref64(x, w, b).cpu()
+        scale = (x.double().abs() @ w.double().abs().t() + (b.double().abs() if b is not None else 0)).cpu()
+        assert _f32_close(out["linear"][i], ref, scale), case
+    for (lengths, tpad, K, N), ys in zip(F32_RAGGED, out["rows"]):
+        x, rowmap, n_real, w, b = _f32_ragged_inputs(lengths, tpad, K, N)
+        rows = rowmap[:n_real].long()
+        xr = x.reshape(-1, K)[rows]
+        for y, bias in zip(ys, (b, None)):
+            assert y.shape == (len(lengths), tpad, N)
+            flat = y.reshape(-1, N)
+            scale = xr.double().abs() @ w.double().abs().t() + (bias.double().abs() if bias is not None else 0)
+            assert _f32_close(flat[rows.cpu()], _ref64(xr, w, bias).cpu(), scale.cpu()), (lengths[:4], tpad, K, N)
+            pad = rowmap[n_real:].long().cpu()
+            assert bool((flat[pad].view(torch.int32) == 0).all()), "a padding row of Y is not +0"
+    for (lengths, P, a, L, K, N), y in zip(F32_GATHER, out["gather"]):
+        base, w, b, x_rows, y_rows, n_real, ln = _f32_gather_inputs(lengths, P, a, L, K, N)
+        xr = base.reshape(-1, K)[x_rows.long() + a]                  # (x_rows count from the slice's first token)
+        scale = xr.double().abs() @ w.double().abs().t() + b.double().abs()
+        assert _f32_close(y[y_rows[:n_real].long().cpu()], _ref64(xr, w, b).cpu(), scale.cpu())
+        assert bool((y[y_rows[n_real:].long().cpu()].view(torch.int32) == 0).all()), "an output row outside the slice is not +0"
+    for shape, s, o in zip(F32_ATTN, out["qk"], out["pv"]):
+        q, k, v, p = (t.double() for t in _f32_attn_inputs(*shape))
+        kt = k.transpose(-1, -2)
+        assert s.shape == shape[:2] + (shape[2], shape[3]) and _f32_close(s, (q @ kt).cpu(), (q.abs() @ kt.abs()).cpu()), shape
+        assert _f32_close(o, (p @ v).cpu(), (p.abs() @ v.abs()).cpu()), shape
+    # prune size: 16 384 sampled entries and the whole last rows / columns (the edge tiles), as the 16-bit kernel's test does
+    for (M, N, K), y in zip(F32_PRUNE, out["prune"]):
+        x, w, b = _f32_prune_inputs(M, N, K)
+        y = y.to(DEV)
+        g = torch.Generator(device=DEV).manual_seed(M)
+
+        def check(rows, cols):
+            xr, wc = x[rows].double(), w[cols].double()
+            ref = (xr * wc).sum(-1) + b[cols].double()
+            scale = (xr.abs() * wc.abs()).sum(-1) + b[cols].double().abs()
+            assert _f32_close(y[rows, cols], ref, scale), (M, N, K)
+        check(torch.randint(0, M, (16384,), generator=g, device=DEV), torch.randint(0, N, (16384,), generator=g, device=DEV))
+        check(torch.arange(M - 40, M, device=DEV).repeat_interleave(N), torch.arange(N, device=DEV).repeat(40))
+        check(torch.randint(0, M, (2048,), generator=g, device=DEV).repeat_interleave(24), torch.arange(N - 24, N, device=DEV).repeat(2048))

@@ -225,3 +225,92 @@ def test_entry_points_refuse_what_they_do_not_implement():
     assert lib.vlmc_sparse_lora_fwd(*args(_lib.F16, 128, 128, 8, 2)) == _lib.VLMC_EINVAL
     assert lib.vlmc_sparse_lora_fwd(*args(_lib.F16, 96, 128, 8, 1)) == _lib.VLMC_EINVAL
     assert b"multiples of 64" in lib.vlmc_last_error()
+
+
+# ---- activation rows per generated W_eff tile (csrc/lora_gemm.hip: pick_bq takes 192 or 256 by the launch's size; VLMC_LORA_BQ forces
+# one): forward and dX run on either, dA / dB always come from the 256-row G kernel.  Every choice must give the same bits.
+BQ_CONFIGS = [(torch.float16, 2.0), (torch.float16, 16 / 3), (torch.bfloat16, 2.0)]    # (s = 2.0 in fp16: the exact-scaling generator)
+BQ_SHAPES = [(128, 64, 16), (320, 192, 8)]
+BQ_MS = [1, 63, 64, 65, 191, 192, 193, 255, 256, 257, 385, 2048]                       # the 192- and 256-row tiles' edges
+BQ_BIG = (4096, 4096, 16, 2048)                                                         # the rule's 256 route (Vicuna-7B q / k / v / o)
+
+
+def _bq_cases():
+    """(config index, out_f, in_f, r, M, sparse): every M for both small shapes under every config, sparse and masked alternating;
+    the big shape once per config."""
+    cases = [(c, *shape, M, (i + c) % 2 == 0) for c in range(len(BQ_CONFIGS)) for shape in BQ_SHAPES for i, M in enumerate(BQ_MS)]
+    return cases + [(c, *BQ_BIG, c != 1) for c in range(len(BQ_CONFIGS))]
+
+
+def _bq_inputs(c, out_f, in_f, r, M, sparse):
+    wd, s = BQ_CONFIGS[c]
+    W, A, B, Mk, b = _layer(out_f, in_f, r, wd, seed=c, bias=True)
+    g = torch.Generator().manual_seed(M * 3 + c)
+    x = torch.randn(M, in_f, generator=g).to(wd)
+    gy = (torch.randn(M, out_f, generator=g) * 0.05).to(wd)
+    return wd, s, W, A, B, Mk, b, x, gy
+
+
+def lora_bq_outputs():
+    """y, dX, dA, dB, dbias of one fused autograd step per case (run once per VLMC_LORA_BQ value in a child process)."""
+    out = []
+    for case in _bq_cases():
+        wd, s, W, A, B, Mk, b, x, gy = _bq_inputs(*case)
+        Ad, Bd, bd = A.to(DEV).requires_grad_(True), B.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
+        xd = x.to(DEV).requires_grad_(True)
+        y = _fused(xd, W.to(DEV), Ad, Bd, Mk.to(DEV), bd, s, case[-1])
+        y.backward(gy.to(DEV))
+        out.append([t.cpu() for t in (y.detach(), xd.grad, Ad.grad, Bd.grad, bd.grad)])
+    return out
+
+
+@pytest.fixture(scope="module")
+def lora_bq(tmp_path_factory):
+    import variant_runs
+    return variant_runs.run_variants(tmp_path_factory.mktemp("lora_bq"), "test_lora_gemm_gpu", "lora_bq_outputs",
+                                     {"default": {}, "192": {"VLMC_LORA_BQ": "192"}, "256": {"VLMC_LORA_BQ": "256"}})
+
+
+def test_rows_per_tile_give_the_same_bits(lora_bq):
+    """VLMC_LORA_BQ = 192 / 256 and the size rule: forward with bias, dX, dA, dB and dbias bit for bit, f16 with the exact and the
+    general scaling, bf16, sparse and masked, M across both tiles' edges and the 4096 x 4096 layer at M = 2048."""
+    import variant_runs
+    variant_runs.assert_variants_agree(lora_bq)
+
+
+@pytest.mark.parametrize("c", range(len(BQ_CONFIGS)))
+def test_rows_per_tile_against_the_oracle_autograd(lora_bq, c):
+    """The 256-row route (forced where the rule takes 192) against `_oracle_autograd`: every entry of the small shapes, 64 rows and
+    64 columns of the 4096 x 4096 layer (complete sub-problems, as test_vicuna_7b_shapes)."""
+    wd = BQ_CONFIGS[c][0]
+    rt = 4e-3 if wd == torch.float16 else 2e-2                      # test_vicuna_7b_shapes (fp16) / the unfused comparison's bf16 bound
+    at = 2e-3 if wd == torch.float16 else rt * 0.25
+
+    def close(got, ref, name, grad=False):
+        got = got.float()
+        if grad:
+            torch.testing.assert_close(got, ref, rtol=4 * ULP[wd], atol=8 * ULP[wd] * ref.abs().max().item(), msg=lambda m: f"{name}: {m}")
+        else:
+            torch.testing.assert_close(got, ref, rtol=rt, atol=at * ref.abs().max().item(), msg=lambda m: f"{name}: {m}")
+    for case, (y, gx, gA, gB, _) in zip(_bq_cases(), lora_bq["256"]):
+        if case[0] != c:
+            continue
+        _, s, W, A, B, Mk, b, x, gy = _bq_inputs(*case)
+        sparse = case[-1]
+        if case[1:4] != BQ_BIG[:3]:
+            yo, gxo, gAo, gBo = _oracle_autograd(x, gy, W, A, B, Mk, s, sparse, wd)
+            close(y, yo + b.float(), f"y {case}")
+            close(gx, gxo, f"dX {case}")
+            close(gA, gAo, f"dA {case}", grad=True)
+            close(gB, gBo, f"dB {case}", grad=True)
+            continue
+        out_f, in_f = W.shape
+        gi = torch.Generator().manual_seed(out_f + in_f + c)
+        J = torch.randperm(out_f, generator=gi)[:64].sort().values
+        yo, _, _, gBo = _oracle_autograd(x, gy[:, J], W[J], A, B[J], Mk[J], s, sparse, wd)
+        close(y[:, J], yo + b[J].float(), "y[:, J]")
+        close(gB[J], gBo, "dB[J]", grad=True)
+        I = torch.randperm(in_f, generator=gi)[:64].sort().values
+        _, gxo, gAo, _ = _oracle_autograd(x[:, I], gy, W[:, I], A[:, I], B, Mk[:, I], s, sparse, wd)
+        close(gx[:, I], gxo, "dX[:, I]")
+        close(gA[:, I], gAo, "dA[:, I]", grad=True)

@@ -83,6 +83,70 @@ def test_sqnorm_strided_rows_and_misaligned_base():
         assert np.array_equal(_bits(got[c]), _bits(OW.act_sqnorm(view[c].cpu())))
 
 
+# ---- the statistics kernel's vector width (csrc/stats.hip: pick_vec takes 1 / 2 / 4 / 8 channels per lane by alignment and size;
+# VLMC_SQNORM_VEC forces one where it is legal and is ignored where it is not): every width gives the oracle's bits.
+SQ_SHAPES = [(128, 4, 8192), (3, 17, 40), (5, 257, 1408), (1, 1, 8), (4, 33, 1001)]    # (128 calls x 8192: the rule's own width 8)
+SQ_VIEWS = [(3, 131), (4, 132), (8, 136)]                                               # channel windows of [4, 20, 200] rows
+SQ_BATCH = [1408, 100, 8, 2048, 1001]                                                  # in_f of the batched jobs (the 4th: a view)
+SQ_CALL_TOKENS = [37, 5, 1, 20, 11, 36]                                                 # a padded group of six ragged calls
+
+
+def _sqnorm_inputs(dtype):
+    g = torch.Generator().manual_seed(17 + {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}[dtype])
+    plain = [((torch.randn(s, generator=g) + 0.1) * 3).to(dtype).to(DEV) for s in SQ_SHAPES]
+    big = (torch.randn(4, 20, 200, generator=g) * 2).to(dtype).to(DEV)
+    views = [big[:, :, a:b] for a, b in SQ_VIEWS]                 # base 3 / 4 / 8 elements in, row stride 200: some widths illegal
+    calls, T = len(SQ_CALL_TOKENS), max(SQ_CALL_TOKENS)
+    xs = [((torch.randn(calls, T, w, generator=g) * 2) + 0.1).to(dtype) for w in SQ_BATCH]
+    for x in xs:
+        for c, t in enumerate(SQ_CALL_TOKENS):
+            x[c, t:] = float("nan")                              # padding rows: nothing may read them
+    xs = [x.to(DEV) for x in xs]
+    xs[3] = torch.cat([torch.zeros(calls, T, 4, dtype=dtype, device=DEV), xs[3]], 2)[:, :, 4:]   # row stride 2052
+    ct = torch.tensor(SQ_CALL_TOKENS, dtype=torch.int32, device=DEV)
+    return plain, views, xs, ct
+
+
+def sqnorm_vec_outputs():
+    """act_sqnorm and act_sqnorm_batch (with call_tokens) on fp16, bf16, fp32 (run once per VLMC_SQNORM_VEC value in a child process)."""
+    ops = _ops()
+    out = {}
+    for dtype in (torch.float16, torch.bfloat16, torch.float32):
+        plain, views, xs, ct = _sqnorm_inputs(dtype)
+        out[str(dtype)] = {"plain": [ops.act_sqnorm(x).cpu() for x in plain + views],
+                           "batch": [o.cpu() for o in ops.act_sqnorm_batch(xs, call_tokens=[ct] * len(xs))],
+                           "batch_full": [o.cpu() for o in ops.act_sqnorm_batch([x[:, :1] for x in xs])]}
+    return out
+
+
+@pytest.fixture(scope="module")
+def sqnorm_vec(tmp_path_factory):
+    import variant_runs
+    return variant_runs.run_variants(tmp_path_factory.mktemp("sqnorm_vec"), "test_wanda_gpu", "sqnorm_vec_outputs",
+                                     {"default": {}, **{str(v): {"VLMC_SQNORM_VEC": str(v)} for v in (1, 2, 4, 8)}})
+
+
+def test_sqnorm_vector_widths_give_the_same_bits(sqnorm_vec):
+    """VLMC_SQNORM_VEC = 1 / 2 / 4 / 8 and the size rule (8 where 128 calls x 8192 channels fill the device), including the shapes
+    and misaligned views where a forced width is illegal and must be ignored."""
+    import variant_runs
+    variant_runs.assert_variants_agree(sqnorm_vec)
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16, torch.float32])
+def test_sqnorm_vector_widths_against_oracle(sqnorm_vec, dtype):
+    plain, views, xs, ct = _sqnorm_inputs(dtype)
+    for label, res in sqnorm_vec.items():
+        out = res[str(dtype)]
+        for x, got in zip(plain + views, out["plain"]):
+            for c in range(x.shape[0]):
+                assert np.array_equal(_bits(got[c].numpy()), _bits(OW.act_sqnorm(x[c].cpu()))), (label, tuple(x.shape), c)
+        for x, got, one in zip(xs, out["batch"], out["batch_full"]):
+            for c, t in enumerate(SQ_CALL_TOKENS):
+                assert np.array_equal(_bits(got[c].numpy()), _bits(OW.act_sqnorm(x[c, :t].cpu()))), (label, x.shape[2], c)
+                assert np.array_equal(_bits(one[c].numpy()), _bits(OW.act_sqnorm(x[c, :1].cpu()))), (label, x.shape[2], c)
+
+
 # ------------------------------------------------------------------- selection --
 def _run_select(W, s, mode, **kw):
     ops = _ops()

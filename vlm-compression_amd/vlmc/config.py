@@ -70,6 +70,7 @@ CROSSCHECK = {
     "VLMC_RMS_NORM": ("1", "0: the language-model blocks' RMS norms run as the model files' seven launches"),
     "VLMC_SDPA_DMA": ("1", "0: K and V of vlmc_sdpa staged through registers"),
     "VLMC_SDPA": ("1", "0: F.scaled_dot_product_attention inside a replayed block left to torch"),
+    "VLMC_ATTN_DMA": ("1", "0: K / V of vlmc_attn_fwd staged through registers"),
     "VLMC_ATTN_MATMUL": ("1", "0: the blocks' batched matmuls left to torch during the replay"),
     "VLMC_ROW_MEAN": ("1", "0: the norms' fp32 mean left to torch during the replay"),
     "VLMC_ATTN_TR": ("1", "0: attn @ v with the operand transposed while writing LDS"),
@@ -107,7 +108,6 @@ INTERNAL = {
     "VLMC_F32_TILE": ("0", "128 / 64 / 32: one tile size for every fp32 GEMM launch (same bits)"),
     "VLMC_LORA_BQ": ("0", "192 / 256: activation rows per generated W_eff tile"), "VLMC_LORA_DBG": ("0", "lora_gemm ablation bits (results invalid)"),
     "VLMC_LORA_RECOMPUTE": ("0", "1: regenerate W_eff in the unfused backward instead of keeping it"),
-    "VLMC_ATTN_DMA": ("1", "0: K / V of vlmc_attn_fwd staged through registers"),
     "VLMC_SGPT_SWEEP_STREAMS": ("4", "streams for the sweeps of a block's independent linears"),
     "VLMC_SGPT_SHARD_LAYERS": ("1", "0: under torch.distributed every rank prunes every linear"),
     "VLMC_SGPT_SYRK_F32": ("0", "1: fp32 activations take the nine-plane SYRK"),

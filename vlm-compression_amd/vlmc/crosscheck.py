@@ -43,6 +43,7 @@ ROUTES = {
     "sgpt_chain": ({"VLMC_SGPT_PERSISTENT": "0"}, "the factorization as a chain of launches per 128 columns instead of one persistent launch"),
     "norm_op_sequence": ({"VLMC_RMS_NORM": "0"}, "the language-model blocks' RMS norms run as the model files' seven launches"),
     "sdpa_register_staging": ({"VLMC_SDPA_DMA": "0"}, "K and V of a head staged into LDS through registers instead of LDS-DMA"),
+    "attn_register_staging": ({"VLMC_ATTN_DMA": "0"}, "K and V of a fused attention (vlmc_attn_fwd) staged into LDS through registers instead of LDS-DMA"),
     "sdpa_library": ({"VLMC_SDPA": "0"}, "F.scaled_dot_product_attention inside a replayed block left to torch"),
     "attn_library": ({"VLMC_ATTN_MATMUL": "0", "VLMC_ROW_MEAN": "0"}, "the blocks' batched matmuls and the norms' mean left to torch during the replay"),
     "attn_transposing_write": ({"VLMC_ATTN_TR": "0"}, "attn @ v with the operand transposed while writing LDS (no ds_read_b64_tr_b16)"),
