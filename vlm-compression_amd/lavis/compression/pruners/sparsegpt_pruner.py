@@ -3,11 +3,23 @@
 (reference: lavis/compression/pruners/sparsegpt_pruner.py:222-497, :500-867, :870-1090).
 
 Same registry names, constructor kwargs and `prune(importance_scores=None,
-keep_indices_or_masks=None) -> (model, sparsity_dict | None)` contract (no `lora_model`
-argument, like the reference).  Quirks kept: calibration stops by BATCH index (`i >= n_samples`,
-:391-393), both towers are pruned whenever their spec is not None (no keep-ratio < 1 test,
-:1021,:1044), the LLM branch walks `...model.decoder.layers` (OPT layout, :1084), no `module.mask`
-is attached (SparseGPT only rewrites the weights).  The arithmetic lives in `vlmc.sparsegpt`.
+keep_indices_or_masks=None) -> (model, sparsity_dict | None)` contract.  Quirks kept: calibration stops by BATCH index
+(`i >= n_samples`, :391-393), both towers are pruned whenever their spec is not None (no keep-ratio < 1 test,
+:1021,:1044), no `module.mask` is attached (SparseGPT only rewrites the weights).  The arithmetic lives in `vlmc.sparsegpt`.
+
+Beyond the reference:
+* `blipt5_sparsegpt_pruner` with a `t5_model_prefix` containing "llm_model" walks
+  `{prefix}{peft_postfix}.model.layers` (InstructBLIP-Vicuna), as the Wanda and DSnoT BLIP pruners do; any other non-T5
+  prefix keeps the reference's OPT walk `...model.decoder.layers` (:1084).  `peft_postfix=""` is accepted.
+* `prune(..., lora_model=False)`.  With True (what the RESSA driver calls, train.py:569) every linear gets the same
+  Hessian, factorization and blocked OBS sweep as without, on the fp32 working copy, but the sweep's keep pattern
+  (the complement of its `mask_out`) goes onto `module.mask` (bool [out, in], True = keep, the SparseLoRA buffer) and
+  `module.weight` is left bit for bit as it was: the reconstruction is discarded.  RESSA's `dense=True` teacher forward
+  reads that same weight tensor (lora.py `Linear.forward`), Wanda and DSnoT never write weights under `lora_model`, and
+  keeping the reconstruction would need a second weight buffer (another checkpoint format).  The calibration forward is
+  `model(batch, vit_dense=..., llm_dense=...)` and a tower whose keep ratio is 1 is skipped, as in the Wanda BLIP pruner
+  (wanda_pruner.py:436-470); the blocks replay with the cached `dense=True`, so every block is calibrated on the dense
+  model's activations.  Layer-sharded runs broadcast the mask from the linear's owner instead of the weight.
 """
 from __future__ import annotations
 
@@ -28,16 +40,16 @@ _KW = dict(prune_spec=None, importance_scores_cache=None, keep_indices_or_masks_
 
 
 class _SparseGPTBlockMixin:
-    def _capture(self, model, dataloader, n_samples, module_to_process, vit, model_prefix=None):
-        return cal.capture_block_inputs(model, dataloader, n_samples, module_to_process,
-                                        lambda m, b, _lora=False: self.forward_to_cache(m, b), False, vit=vit,
+    def _capture(self, model, dataloader, n_samples, module_to_process, vit, model_prefix=None, lora_model=False):
+        return cal.capture_block_inputs(model, dataloader, n_samples, module_to_process, self.forward_to_cache, lora_model, vit=vit,
                                         model_prefix=model_prefix, count_batches=True, done_towers=getattr(self, "_done_towers", None),
                                         proxy_cache=self.__dict__.setdefault("_proxy_cache", {}))
 
-    def _sparsegpt_block(self, i, subset, run_pass, n_inps, module_to_process, sparsity_ratio):
+    def _sparsegpt_block(self, i, subset, run_pass, n_inps, module_to_process, sparsity_ratio, lora_model=False):
         """Hooks -> one dense pass -> prune every linear (sparsegpt_pruner.py:405-459).  Linears that receive the
         very same tensor (q/k/v, wi_0/wi_1, cross-attention k/v) have bit-identical Hessians: they share ONE
-        accumulator (one GEMM per hook input instead of one per linear) and ONE Cholesky chain."""
+        accumulator (one GEMM per hook input instead of one per linear) and ONE Cholesky chain.  `lora_model`: the
+        sweeps' keep masks go onto `module.mask`, the weights stay (module docstring)."""
         from vlmc import sparsegpt
         wrapped, fed = {}, {}            # linear name -> accumulator; input signature -> accumulator fed in this forward
 
@@ -84,18 +96,25 @@ class _SparseGPTBlockMixin:
         for name in mine:
             assert wrapped[name].nsamples == n_inps                                # :442
             by_acc.setdefault(id(wrapped[name]), []).append(name)
+        masks = {}
+        only = dict(mask_only=True) if lora_model else {}          # (the prune-only calls keep their exact arguments)
+
         def sweep(names):
             acc = wrapped[names[0]]
             keys = [f"{module_to_process}.{i}.{n}.weight" for n in names]
             same = len({(subset[n].weight.dtype, subset[n].weight.shape[1]) for n in names}) == 1
             if len(names) > 1 and same and "U" in acc.factor_cache and sparsegpt.stacked_sweeps_enabled():
                 # linears fed the same tensor share the factor: ONE column sweep over their stacked rows
-                sparsegpt.fasterprune_group([subset[n] for n in names], [sparsity_ratio[k] for k in keys], acc.factor_cache,
-                                            prune_n=self.prune_n, prune_m=self.prune_m, blocksize=128, score_sink=scores)
+                keep = sparsegpt.fasterprune_group([subset[n] for n in names], [sparsity_ratio[k] for k in keys], acc.factor_cache,
+                                                   prune_n=self.prune_n, prune_m=self.prune_m, blocksize=128, score_sink=scores, **only)
+                if lora_model:
+                    masks.update(zip(names, keep))
                 return
             for name, key in zip(names, keys):
-                sparsegpt.fasterprune(subset[name], acc.H, sparsity_ratio[key], prune_n=self.prune_n, prune_m=self.prune_m,
-                                      percdamp=0.01, blocksize=128, factor_cache=acc.factor_cache, score_sink=scores)
+                keep = sparsegpt.fasterprune(subset[name], acc.H, sparsity_ratio[key], prune_n=self.prune_n, prune_m=self.prune_m,
+                                             percdamp=0.01, blocksize=128, factor_cache=acc.factor_cache, score_sink=scores, **only)
+                if lora_model:
+                    masks[name] = keep
 
         # The sweeps of linears with DIFFERENT inputs are independent chains of (cols / 128) x [latency-bound sweep kernel +
         # trailing GEMM] (the reference prunes them one after the other, :430-446): each chain on a stream of its own, the
@@ -124,11 +143,15 @@ class _SparseGPTBlockMixin:
                 main.wait_stream(st)
             for name in mine:                                   # made on a side stream, used on the caller's from here on
                 subset[name].weight.data.record_stream(main)
+                if name in masks:
+                    masks[name].record_stream(main)
             for _w, sc in scores[n0:]:
                 sc.record_stream(main)
+        for name, keep in masks.items():
+            setattr(subset[name], "mask", keep)                 # True = keep: the SparseLoRA buffer
         if owner is not None:
             _flush_score_backlog(self)                                             # (the exchange sends the scores along)
-            _exchange_pruned(subset, owner, rank)
+            _exchange_pruned(subset, owner, rank, masks=lora_model)
         for acc in unique:
             acc.free()
 
@@ -165,8 +188,9 @@ def _shard_linears(subset, wrapped):
     return owner
 
 
-def _exchange_pruned(subset, owner, rank):
-    """Every linear's pruned weights (and its importance score) travel from the rank that pruned it to all others."""
+def _exchange_pruned(subset, owner, rank, masks=False):
+    """Every linear's pruned weights (and its importance score) travel from the rank that pruned it to all others;
+    `masks` (lora_model): its keep mask instead of the weights, which no rank has changed."""
     import torch.distributed as dist
     names = list(subset)
     dev = subset[names[0]].weight.device
@@ -175,6 +199,11 @@ def _exchange_pruned(subset, owner, rank):
         w = subset[name].weight
         if owner[name] == rank:
             scores[k] = float(getattr(w, "importance_score", 0.0))
+        if masks:
+            if owner[name] != rank:
+                subset[name].mask = torch.empty(w.shape, dtype=torch.bool, device=dev)
+            dist.broadcast(subset[name].mask.view(torch.uint8), src=owner[name])      # (as bytes: every backend takes them)
+            continue
         data = w.data if w.data.is_contiguous() else w.data.contiguous()
         dist.broadcast(data, src=owner[name])
         if data is not w.data:
@@ -210,22 +239,25 @@ class T5LayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
         kw = dict(_KW); kw.update({k: v for k, v in kwargs.items() if k in _KW})
         super().__init__(model=model, data_loader=data_loader, model_prefix=model_prefix, **kw)
 
-    def forward_to_cache(self, model, batch):
+    def forward_to_cache(self, model, batch, lora_model=False):
         return model(batch)
+
+    def get_sparsity(self, original_sparsity, sparsity_ratio_granularity=None):
+        return uniform_or_layer_sparsity(self, original_sparsity, sparsity_ratio_granularity)
 
     @print_time
     def _prune(self, model, dataloader, device, model_prefix, module_to_process="encoder.block", n_samples=64,
-               sparsity_ratio=0.5):
+               sparsity_ratio=0.5, lora_model=False):
         cfg = getattr(model, model_prefix).config
         use_cache, cfg.use_cache = cfg.use_cache, False
         print("loading calibdation data")
         with torch.no_grad():
             inps, outs, caches = self._capture(model, dataloader, n_samples, module_to_process, vit=False,
-                                               model_prefix=self.model_prefix)
+                                               model_prefix=self.model_prefix, lora_model=lora_model)
         n_inps = len(inps) * cal.calibration_shard()[1]
 
         def prune_block(i, layer, subset, run_pass, state):
-            self._sparsegpt_block(i, subset, run_pass, n_inps, module_to_process, sparsity_ratio)
+            self._sparsegpt_block(i, subset, run_pass, n_inps, module_to_process, sparsity_ratio, lora_model)
 
         try:
             cal.walk_blocks(model, inps, outs, caches, module_to_process, n_samples,
@@ -236,6 +268,24 @@ class T5LayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
         cal.release_tower_memory()
         return model
 
+    @cal.quiet_gc
+    @print_time
+    def prune(self, importance_scores=None, keep_indices_or_masks=None, lora_model=False):
+        """Encoder, then decoder (sparsegpt_pruner.py:511-543)."""
+        print("In: ", self.pruner_name)
+        dtype_record, requires_grad_record, device = self.model_setup_and_record_attributes(self.model)
+        if self.prune_spec is None:
+            return self.model, None
+        _, keep_ratio, _, _ = self.convert_spec_to_list(self.prune_spec)
+        sparsity_dict = self.get_sparsity(1 - keep_ratio, sparsity_ratio_granularity=self.sparsity_ratio_granularity)
+        for side in ("encoder", "decoder"):
+            self.model = self._prune(self.model, self.data_loader, device, model_prefix=self.model_prefix,
+                                     module_to_process=f"{self.model_prefix}.{side}.block", n_samples=self.num_samples,
+                                     sparsity_ratio=sparsity_dict, lora_model=lora_model)
+        self.model_reset(self.model, dtype_record, requires_grad_record, device)
+        _release_factor_caches()
+        return self.model, sparsity_dict
+
 
 @registry.register_pruner("vit_sparsegpt_pruner")
 class VITLayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
@@ -245,18 +295,20 @@ class VITLayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
         kw = dict(_KW); kw.update({k: v for k, v in kwargs.items() if k in _KW})
         super().__init__(model=model, data_loader=data_loader, model_prefix=model_prefix, **kw)
 
-    def forward_to_cache(self, model, batch):
+    def forward_to_cache(self, model, batch, lora_model=False):
         return model.encode_image(batch["image"])
+
+    get_sparsity = T5LayerSparseGPTPruner.get_sparsity
 
     @print_time
     def _prune(self, model, dataloader, device, model_prefix, module_to_process="encoder.block", n_samples=64,
-               sparsity_ratio=0.5):
+               sparsity_ratio=0.5, lora_model=False):
         with torch.no_grad():
-            inps, outs, caches = self._capture(model, dataloader, n_samples, module_to_process, vit=True)
+            inps, outs, caches = self._capture(model, dataloader, n_samples, module_to_process, vit=True, lora_model=lora_model)
         n_inps = len(inps) * cal.calibration_shard()[1]
 
         def prune_block(i, layer, subset, run_pass, state):
-            self._sparsegpt_block(i, subset, run_pass, n_inps, module_to_process, sparsity_ratio)
+            self._sparsegpt_block(i, subset, run_pass, n_inps, module_to_process, sparsity_ratio, lora_model)
 
         try:
             cal.walk_blocks(model, inps, outs, caches, module_to_process, n_samples, lambda: model.maybe_autocast(),
@@ -266,13 +318,36 @@ class VITLayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
         cal.release_tower_memory()
         return model
 
+    @cal.quiet_gc
+    @print_time
+    def prune(self, importance_scores=None, keep_indices_or_masks=None, lora_model=False):
+        """The ViT blocks (sparsegpt_pruner.py:838-864)."""
+        print("In: ", self.pruner_name)
+        dtype_record, requires_grad_record, device = self.model_setup_and_record_attributes(self.model)
+        if self.prune_spec is None:
+            return self.model, None
+        _, keep_ratio, _, _ = self.convert_spec_to_list(self.prune_spec)
+        sparsity_dict = self.get_sparsity(1 - keep_ratio, sparsity_ratio_granularity=self.sparsity_ratio_granularity)
+        self.model = self._prune(self.model, self.data_loader, device, model_prefix=self.model_prefix,
+                                 module_to_process=f"{self.model_prefix}.blocks", n_samples=self.num_samples,
+                                 sparsity_ratio=sparsity_dict, lora_model=lora_model)
+        self.model_reset(self.model, dtype_record, requires_grad_record, device)
+        _release_factor_caches()
+        return self.model, sparsity_dict
+
+
+def _release_factor_caches():
+    from vlmc import sparsegpt as _sg
+    _sg.release_caches()          # factorization graphs + n x n work buffers are not kept past the prune
+
 
 @registry.register_pruner("blipt5_sparsegpt_pruner")
 class BLIPT5LayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
     pruner_name = "blipt5_sparsegpt_pruner"
 
     def __init__(self, model, data_loader, t5_prune_spec=None, vit_prune_spec=None, t5_pruning_method=None,
-                 vit_pruning_method=None, t5_model_prefix="t5_model", vit_model_prefix="visual_encoder", **kwargs):
+                 vit_pruning_method=None, t5_model_prefix="t5_model", vit_model_prefix="visual_encoder", peft_postfix="",
+                 **kwargs):
         kw = dict(_KW); kw.update({k: v for k, v in kwargs.items() if k in _KW})
         kw["prune_spec"] = None
         super().__init__(model=model, data_loader=data_loader, model_prefix=f"{vit_model_prefix}+{t5_model_prefix}", **kw)
@@ -282,17 +357,31 @@ class BLIPT5LayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
         assert vit_pruning_method is not None
         self.t5_model_prefix = t5_model_prefix
         self.vit_model_prefix = vit_model_prefix
+        self.peft_postfix = peft_postfix
+        self.vit_dense = True
+        self.llm_dense = True
 
     def get_sparsity(self, original_sparsity, sparsity_ratio_granularity=None):
         return uniform_or_layer_sparsity(self, original_sparsity, sparsity_ratio_granularity)
 
-    def forward_to_cache(self, model, batch):
+    def forward_to_cache(self, model, batch, lora_model=False):
+        if lora_model:
+            return model(batch, vit_dense=self.vit_dense, llm_dense=self.llm_dense)      # (wanda_pruner.py:941-945)
         return model(batch)
+
+    def _llm_layers(self):
+        """The language model's block list: T5 has two (handled by the caller), InstructBLIP-Vicuna's LLaMA keeps its layers at
+        `{prefix}{peft_postfix}.model.layers` (wanda_pruner.py:1031-1038), anything else the reference's OPT walk (:1084)."""
+        if "llm_model" in self.t5_model_prefix:
+            return f"{self.t5_model_prefix}{self.peft_postfix}.model.layers"
+        return f"{self.t5_model_prefix}.model.decoder.layers"
 
     @cal.quiet_gc
     @print_time
-    def prune(self, importance_scores=None, keep_indices_or_masks=None):
+    def prune(self, importance_scores=None, keep_indices_or_masks=None, lora_model=False):
         print("In: ", self.pruner_name)
+        if lora_model:
+            return self._prune_masks_only()
         dtype_record, requires_grad_record, device = self.model_setup_and_record_attributes(self.model)
         global_sparsity_dict = None
         if self.sparsity_ratio_granularity is not None:
@@ -322,9 +411,43 @@ class BLIPT5LayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
             else:
                 self.model = T5LayerSparseGPTPruner._prune(self, self.model, self.data_loader, device,
                                                            model_prefix=self.t5_model_prefix,
-                                                           module_to_process=f"{self.t5_model_prefix}.model.decoder.layers",
+                                                           module_to_process=self._llm_layers(),
                                                            n_samples=self.num_samples, sparsity_ratio=sd)
         self.model_reset(self.model, dtype_record, requires_grad_record, device)
-        from vlmc import sparsegpt as _sg
-        _sg.release_caches()          # factorization graphs + n x n work buffers are not kept past the prune
+        _release_factor_caches()
+        return self.model, global_sparsity_dict
+
+    def _prune_masks_only(self):
+        """`prune(lora_model=True)`: the towers and dense flags of the Wanda BLIP pruner (wanda_pruner.py:436-470) -- a tower is
+        pruned only when its keep ratio is below 1, and its calibration forward is dense exactly then -- with SparseGPT's
+        sweeps deciding every `module.mask`; no weight is written."""
+        dtype_record, requires_grad_record, device = self.model_setup_and_record_attributes(self.model)
+        keep = {}
+        for tower, spec in (("vit", self.vit_prune_spec), ("llm", self.t5_prune_spec)):
+            keep[tower] = None if spec is None else self.convert_spec_to_list(spec)[1]
+        global_sparsity_dict = None
+        if self.sparsity_ratio_granularity not in [None, "none"]:
+            assert keep["vit"] == keep["llm"]
+            global_sparsity_dict = self.get_sparsity(1 - keep["llm"], sparsity_ratio_granularity=self.sparsity_ratio_granularity)
+        prune_vit = keep["vit"] is not None and float(keep["vit"]) < 1.
+        prune_llm = keep["llm"] is not None and float(keep["llm"]) < 1.
+        self.vit_dense, self.llm_dense = prune_vit, prune_llm
+
+        def tower(cls, module_to_process, model_prefix, ratio):
+            sd = global_sparsity_dict if global_sparsity_dict is not None else self.get_sparsity(1 - ratio, None)
+            self.model = cls._prune(self, self.model, self.data_loader, device, model_prefix=model_prefix,
+                                    module_to_process=module_to_process, n_samples=self.num_samples, sparsity_ratio=sd,
+                                    lora_model=True)
+            self._done_towers = getattr(self, "_done_towers", []) + [module_to_process]
+
+        if prune_vit:
+            tower(VITLayerSparseGPTPruner, f"{self.vit_model_prefix}.blocks", self.vit_model_prefix, keep["vit"])
+        if prune_llm:
+            if "t5_model" in self.t5_model_prefix:
+                for side in ("encoder", "decoder"):
+                    tower(T5LayerSparseGPTPruner, f"{self.t5_model_prefix}.{side}.block", self.t5_model_prefix, keep["llm"])
+            else:
+                tower(T5LayerSparseGPTPruner, self._llm_layers(), self.t5_model_prefix, keep["llm"])
+        self.model_reset(self.model, dtype_record, requires_grad_record, device)
+        _release_factor_caches()
         return self.model, global_sparsity_dict

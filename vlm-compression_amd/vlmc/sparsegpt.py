@@ -659,10 +659,12 @@ def select_sweep_block(W: torch.Tensor, i1: int, i2: int, U: torch.Tensor, rows_
 
 @torch.no_grad()
 def fasterprune(layer, H: torch.Tensor, sparsity, prune_n=0, prune_m=0, blocksize=128, percdamp=0.01, return_mask=False,
-                factor_cache=None, score_sink=None):
+                factor_cache=None, score_sink=None, mask_only=False):
     """`SparseGPT.fasterprune` (:81-215): prunes `layer.weight` in place, sets
     `weight.importance_score`.  H is consumed.  `factor_cache` (a dict owned by the caller, one per distinct
-    Hessian) lets linears with the same input reuse the factorization -- bit-identical to recomputing it."""
+    Hessian) lets linears with the same input reuse the factorization -- bit-identical to recomputing it.
+    `mask_only` (the pruners' `lora_model=True`): the same sweep on the fp32 working copy, but `layer.weight` is left as it
+    is and the keep mask (True = keep, the complement of the sweep's `mask_out`) is returned; the reconstruction is dropped."""
     W = layer.weight.data.clone().float()
     if factor_cache is not None and "U" in factor_cache:
         U, dead = factor_cache["U"], factor_cache["dead"]
@@ -674,7 +676,7 @@ def fasterprune(layer, H: torch.Tensor, sparsity, prune_n=0, prune_m=0, blocksiz
     diag = torch.diag(U)
     score_mean = (W ** 2 / diag.reshape(1, -1) ** 2).abs().mean()
     rows, cols = W.shape
-    pruned = torch.zeros((rows, cols), dtype=torch.bool, device=W.device) if return_mask else None
+    pruned = torch.zeros((rows, cols), dtype=torch.bool, device=W.device) if (return_mask or mask_only) else None
     fused = prune_n == 0 and _SELECT_THRESHOLD and select_sweep_usable([rows], W.device)
     whole = _BLOCK_LOOP and (prune_n != 0 or fused)
     if whole:                                                                              # :167-212, every block, from one call
@@ -705,6 +707,8 @@ def fasterprune(layer, H: torch.Tensor, sparsity, prune_n=0, prune_m=0, blocksiz
         setattr(layer.weight, "importance_score", score_mean.item())                       # :165
     else:
         score_sink.append((layer.weight, score_mean))              # read back by the caller, all linears of a block at once
+    if mask_only:
+        return torch.logical_not(pruned)
     layer.weight.data = W.reshape(layer.weight.shape).to(layer.weight.data.dtype)          # :215
     return pruned
 
@@ -715,14 +719,14 @@ def stacked_sweeps_enabled():
 
 
 @torch.no_grad()
-def fasterprune_group(layers, sparsities, factor_cache, prune_n=0, prune_m=0, blocksize=128, score_sink=None):
+def fasterprune_group(layers, sparsities, factor_cache, prune_n=0, prune_m=0, blocksize=128, score_sink=None, mask_only=False):
     """`fasterprune` for linears that share ONE factor (q / k / v, wi_0 / wi_1, a cross-attention's k / v: fed the same tensor,
     hence the same Hessian): their weights are stacked along the rows and swept together -- the column sweep, the
     compensation of the columns to the right and the trailing update are row-wise (sparsegpt_pruner.py:186-210), so a
     row gets what its own sweep would give it, while the launches per 128 columns (~11 in unstructured mode) are issued once
     for the group instead of once per linear.  The per-block threshold stays PER LINEAR (`sort(tmp.flatten())[k]` over the
     linear's own [rows, 128] block, :183-185): one multi-tensor radix select with a scope per linear.  `factor_cache` must
-    hold the factor (factorize_many)."""
+    hold the factor (factorize_many).  `mask_only`: as in `fasterprune` -- the weights stay, the list of keep masks is returned."""
     U, dead = factor_cache["U"], factor_cache["dead"]
     rows = [l.weight.shape[0] for l in layers]
     cols = layers[0].weight.shape[1]
@@ -736,8 +740,9 @@ def fasterprune_group(layers, sparsities, factor_cache, prune_n=0, prune_m=0, bl
     means = [(W[bounds[i]:bounds[i + 1]] ** 2 / dsq).abs().mean() for i in range(len(layers))]
     fused = prune_n == 0 and _SELECT_THRESHOLD and select_sweep_usable(rows, W.device)
     whole = _BLOCK_LOOP and (prune_n != 0 or fused)
+    pruned = torch.zeros((W.shape[0], cols), dtype=torch.bool, device=W.device) if mask_only else None
     if whole:                                                                              # :167-212, every block, from one call
-        prune_blocks(W, U, blocksize, prune_n, prune_m, rows, sparsities, None)
+        prune_blocks(W, U, blocksize, prune_n, prune_m, rows, sparsities, pruned)
     keep = torch.empty((W.shape[0], min(blocksize, cols)), dtype=torch.bool, device=W.device) if (prune_n == 0 and not whole) else None
     err = None if whole else torch.empty((W.shape[0], min(blocksize, cols)), dtype=torch.float32, device=W.device)
     for i1 in (() if whole else range(0, cols, blocksize)):
@@ -745,7 +750,7 @@ def fasterprune_group(layers, sparsities, factor_cache, prune_n=0, prune_m=0, bl
         mask1 = None
         if fused:                                                                          # :183-205 in one launch, a scope per linear
             ranks = [min(int(r * (i2 - i1) * sp), r * (i2 - i1) - 1) for r, sp in zip(rows, sparsities)]
-            select_sweep_block(W, i1, i2, U, rows, ranks, err, None)
+            select_sweep_block(W, i1, i2, U, rows, ranks, err, pruned)
             trailing_update(W, i2, cols, err, U, i1, i2)                                   # :210
             continue
         if prune_n == 0:
@@ -756,14 +761,17 @@ def fasterprune_group(layers, sparsities, factor_cache, prune_n=0, prune_m=0, bl
                              scope_ks=[int(p.numel() * sp) + 1 for p, sp in zip(parts, sparsities)], scores=parts,
                              apply_weights=False, keeps=[kb[bounds[i]:bounds[i + 1]] for i in range(len(layers))])
             mask1 = torch.logical_not(kb)
-        sweep_block(W, i1, i2, U, mask1, prune_n, prune_m, err, None)
+        sweep_block(W, i1, i2, U, mask1, prune_n, prune_m, err, pruned)
         trailing_update(W, i2, cols, err, U, i1, i2)                                       # :210
     for i, layer in enumerate(layers):
         if score_sink is None:
             setattr(layer.weight, "importance_score", means[i].item())                     # :165
         else:
             score_sink.append((layer.weight, means[i]))
-        layer.weight.data = W[bounds[i]:bounds[i + 1]].reshape(layer.weight.shape).to(layer.weight.data.dtype)   # :215
+        if not mask_only:
+            layer.weight.data = W[bounds[i]:bounds[i + 1]].reshape(layer.weight.shape).to(layer.weight.data.dtype)   # :215
+    if mask_only:
+        return [torch.logical_not(pruned[bounds[i]:bounds[i + 1]]) for i in range(len(layers))]
 
 
 def flush_scores(score_sink):
