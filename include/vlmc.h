@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VLMC_ABI_VERSION 21
+#define VLMC_ABI_VERSION 22
 
 #define VLMC_OK 0
 #define VLMC_EINVAL (-1)     /* bad argument (shape, dtype, alignment, null pointer) */
@@ -380,6 +380,41 @@ int vlmc_attn_fwd_lens(const void *Q, const void *K, const void *V, void *O, int
                        int64_t Tk, int64_t head_dim, const int64_t *q_strides, const int64_t *k_strides, const int64_t *v_strides,
                        int has_mul, float mul, const void *add0, const int64_t *add0_strides, const void *add1,
                        const int64_t *add1_strides, const int32_t *q_len, const int32_t *k_len, void *stream);
+
+/* vlmc_attn_fwd_lens with the clamp of the reference's LLaMA attention between the addends and the softmax
+ * (modeling_llama.py:235-236: `attn_weights = attn_weights + attention_mask; attn_weights = torch.max(attn_weights,
+ * torch.tensor(torch.finfo(attn_weights.dtype).min))` -- the causal and the padding mask are both the dtype's minimum and are ADDED,
+ * so a padded, causally hidden key carries -inf in fp16):  s = max(s, clamp_min) on the score already rounded to the dtype, NaN kept
+ * as torch.maximum keeps it.  clamp_min: a finite value OF THE DTYPE (torch casts the 0-dim bound to the tensor's dtype); add0 is
+ * required (the clamp follows an addend).  Everything else -- operands, strides, q_len / k_len (either may be NULL), the rounding points,
+ * the output layout -- as vlmc_attn_fwd_lens, whose bits (and vlmc_attn_fwd's) do not change: the step exists in instantiations of
+ * its own.  Equal, bit for bit, to vlmc_attn_matmul, torch's `/`, `+`, `torch.max`, vlmc_softmax_rows, vlmc_attn_matmul
+ * (tests/test_attn_clamp_gpu.py).                                                                                                */
+int vlmc_attn_fwd_clamp(const void *Q, const void *K, const void *V, void *O, int dtype, int64_t batch, int64_t heads, int64_t Tq,
+                        int64_t Tk, int64_t head_dim, const int64_t *q_strides, const int64_t *k_strides, const int64_t *v_strides,
+                        int has_mul, float mul, const void *add0, const int64_t *add0_strides, const void *add1,
+                        const int64_t *add1_strides, float clamp_min, const int32_t *q_len, const int32_t *k_len, void *stream);
+
+/* ---- the rotary position embedding of a LLaMA attention, q and k in one launch ----------------------------------------------
+ * Replaces `apply_rotary_pos_emb(q, k, cos, sin, position_ids)`, modeling_llama.py:126-140 (with `rotate_half`, :126-130): two
+ * `repeat`s, two `torch.gather`s by position_ids, and per operand two slices, a negation, a `cat`, two products and a sum -- ~16
+ * launches and ~10 passes over [batch, heads, T, head_dim] tensors per layer and forward.
+ *     out[b, h, t, :] = wd( wd(x[b, h, t, :] * cos[p]) + wd(rotate_half(x[b, h, t, :]) * sin[p]) ),   p = position_ids[b, t]
+ * products and sum in fp32, each rounded once to the dtype (wd) where the tensor op rounds; the negation inside rotate_half is exact:
+ * the bits of the op sequence (tests/test_rope_gpu.py).  q, k [batch, heads, T, head_dim] read in place through ELEMENT strides
+ * {batch, head, token} (head_dim stride 1: views of a grouped q / k / v launch); q_out, k_out written through out_strides {batch, head,
+ * token} (both the same; a [batch, T, heads, head_dim] buffer is what vlmc_attn_fwd* then reads in place); cos, sin: 16-bit tables
+ * [positions, head_dim] of the same dtype, row stride table_ld; position_ids: device int64, element strides {pos_stride_b, pos_stride_t}
+ * (pos_stride_b = 0: one [1, T] row for every batch entry).  q_len: NULL or device int32 [batch] as in vlmc_attn_fwd_lens: rows
+ * t >= q_len[b] are not read and are written as ZEROS.  A position outside [0, positions) is never used as an index: the row is
+ * written as zeros and bit 0 of *status (device int32, may be NULL, zeroed by the caller) is set; vlmc_rope_status copies the word to the
+ * host (it synchronises the stream) and returns VLMC_EINVAL with an error string if it is set.  head_dim: a multiple of 8, at most 128.
+ * The outputs must not alias the inputs (a row's partner half is read after other lanes may have written).                      */
+int vlmc_rope(const void *q, const void *k, void *q_out, void *k_out, int dtype, int64_t batch, int64_t heads, int64_t T,
+              int64_t head_dim, const int64_t *q_strides, const int64_t *k_strides, const int64_t *out_strides, const void *cos,
+              const void *sin, int64_t positions, int64_t table_ld, const int64_t *position_ids, int64_t pos_stride_b,
+              int64_t pos_stride_t, const int32_t *q_len, int32_t *status, void *stream);
+int vlmc_rope_status(const int32_t *status, void *stream);
 
 /* ---- the RMS norm of a language-model block in one launch ---------------------------------------------
  * Replaces the op sequence of transformers' T5LayerNorm.forward / LlamaRMSNorm.forward inside a replayed block

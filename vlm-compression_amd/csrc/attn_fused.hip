@@ -21,10 +21,20 @@ extern "C" int vlmc_attn_fwd(const void *Q, const void *K, const void *V, void *
                               add0_strides, add1, add1_strides, nullptr, nullptr, stream);
 }
 
-extern "C" int vlmc_attn_fwd_lens(const void *Q, const void *K, const void *V, void *O, int dtype, int64_t batch, int64_t heads, int64_t Tq,
-                                  int64_t Tk, int64_t head_dim, const int64_t *q_strides, const int64_t *k_strides,
-                                  const int64_t *v_strides, int has_mul, float mul, const void *add0, const int64_t *add0_strides,
-                                  const void *add1, const int64_t *add1_strides, const int32_t *q_len, const int32_t *k_len, void *stream) {
+// the bound of the clamp is a VALUE OF THE DTYPE (torch casts the 0-dim bound to the tensor's dtype): finite, and unchanged by one rounding
+static bool attn_bound_is_of_dtype(int dtype, float v) {
+    if (!std::isfinite(v)) return false;
+    if (dtype == VLMC_F16) return float(_Float16(v)) == v;
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    return (u & 0xFFFFu) == 0;
+}
+
+static int attn_fwd_impl(const void *Q, const void *K, const void *V, void *O, int dtype, int64_t batch, int64_t heads, int64_t Tq,
+                         int64_t Tk, int64_t head_dim, const int64_t *q_strides, const int64_t *k_strides,
+                         const int64_t *v_strides, int has_mul, float mul, const void *add0, const int64_t *add0_strides,
+                         const void *add1, const int64_t *add1_strides, bool has_clamp, float clamp_min, const int32_t *q_len,
+                         const int32_t *k_len, void *stream) {
     VLMC_REQUIRE(dtype == VLMC_F16 || dtype == VLMC_BF16, "vlmc_attn_fwd: dtype must be VLMC_F16 or VLMC_BF16");
     VLMC_REQUIRE(Q && K && V && O && q_strides && k_strides && v_strides, "vlmc_attn_fwd: null pointer");
     VLMC_REQUIRE(batch > 0 && heads > 0 && Tq > 0 && Tk > 0, "vlmc_attn_fwd: empty problem");
@@ -62,6 +72,11 @@ extern "C" int vlmc_attn_fwd_lens(const void *Q, const void *K, const void *V, v
     }
     a.H = int(heads), a.Tq = int(Tq), a.Tk = int(Tk), a.d = int(head_dim);
     a.has_mul = has_mul, a.mul = mul;
+    if (has_clamp) {
+        VLMC_REQUIRE(add0 != nullptr, "vlmc_attn_fwd_clamp: the clamp follows an addend (add0 is null)");
+        VLMC_REQUIRE(attn_bound_is_of_dtype(dtype, clamp_min), "vlmc_attn_fwd_clamp: clamp_min must be a finite value of the dtype");
+        a.clamp_min = clamp_min;
+    }
     VLMC_REQUIRE(k_len == nullptr || add0 != nullptr, "vlmc_attn_fwd_lens: k_len needs an addend that masks the keys behind it");
     a.qlen = q_len, a.klen = k_len;
     // a head's queries on several workgroups once there are many (each stages K and V again): blocks of 16 queries, ~6 per wave
@@ -77,9 +92,28 @@ extern "C" int vlmc_attn_fwd_lens(const void *Q, const void *K, const void *V, v
     const int ds = int((head_dim + 31) / 32);
     const int nadd = add1 ? 2 : add0 ? 1 : 0;
     const int64_t bh = batch * heads;
-    const int rc = dtype == VLMC_F16 ? (nadd == 0 ? attn_dispatch_f16_0(a, bh, ds, s) : nadd == 1 ? attn_dispatch_f16_1(a, bh, ds, s) : attn_dispatch_f16_2(a, bh, ds, s))
+    const int rc = has_clamp ? (dtype == VLMC_F16 ? (nadd == 1 ? attn_dispatch_clamp_f16_1(a, bh, ds, s) : attn_dispatch_clamp_f16_2(a, bh, ds, s))
+                                                  : (nadd == 1 ? attn_dispatch_clamp_bf16_1(a, bh, ds, s) : attn_dispatch_clamp_bf16_2(a, bh, ds, s)))
+                   : dtype == VLMC_F16 ? (nadd == 0 ? attn_dispatch_f16_0(a, bh, ds, s) : nadd == 1 ? attn_dispatch_f16_1(a, bh, ds, s) : attn_dispatch_f16_2(a, bh, ds, s))
                                      : (nadd == 0 ? attn_dispatch_bf16_0(a, bh, ds, s) : nadd == 1 ? attn_dispatch_bf16_1(a, bh, ds, s) : attn_dispatch_bf16_2(a, bh, ds, s));
     if (rc != VLMC_OK) return rc;
     VLMC_HIP_CHECK_LAUNCH("vlmc_attn_fwd");
     return VLMC_OK;
+}
+
+extern "C" int vlmc_attn_fwd_lens(const void *Q, const void *K, const void *V, void *O, int dtype, int64_t batch, int64_t heads, int64_t Tq,
+                                  int64_t Tk, int64_t head_dim, const int64_t *q_strides, const int64_t *k_strides,
+                                  const int64_t *v_strides, int has_mul, float mul, const void *add0, const int64_t *add0_strides,
+                                  const void *add1, const int64_t *add1_strides, const int32_t *q_len, const int32_t *k_len, void *stream) {
+    return attn_fwd_impl(Q, K, V, O, dtype, batch, heads, Tq, Tk, head_dim, q_strides, k_strides, v_strides, has_mul, mul, add0, add0_strides,
+                         add1, add1_strides, false, 0.f, q_len, k_len, stream);
+}
+
+extern "C" int vlmc_attn_fwd_clamp(const void *Q, const void *K, const void *V, void *O, int dtype, int64_t batch, int64_t heads, int64_t Tq,
+                                   int64_t Tk, int64_t head_dim, const int64_t *q_strides, const int64_t *k_strides,
+                                   const int64_t *v_strides, int has_mul, float mul, const void *add0, const int64_t *add0_strides,
+                                   const void *add1, const int64_t *add1_strides, float clamp_min, const int32_t *q_len,
+                                   const int32_t *k_len, void *stream) {
+    return attn_fwd_impl(Q, K, V, O, dtype, batch, heads, Tq, Tk, head_dim, q_strides, k_strides, v_strides, has_mul, mul, add0, add0_strides,
+                         add1, add1_strides, true, clamp_min, q_len, k_len, stream);
 }

@@ -43,6 +43,7 @@ struct AttnArgs {
     int dma;                    // K and V rows are 16-byte aligned: staged by LDS-DMA
     int has_mul;
     float mul;
+    float clamp_min;            // CLAMP instantiations (vlmc_attn_fwd_clamp): the lower bound of the scores after the addends, a value of the dtype
     // a PADDED group of ragged samples (vlmc_attn_fwd_lens), either may be NULL: klen[b] = the keys of batch entry b that are real -- the
     // caller vouches that every key behind them is masked out by an addend (probability exactly 0): their tiles are neither staged nor
     // multiplied; qlen[b] = its real queries: the rows behind them are written as zeros, not computed
@@ -83,7 +84,9 @@ __device__ __forceinline__ AU16x4 attn_bias4(const uint16_t *row, int key0, int 
 // per workgroup: 8 where a head's K and V leave room for one workgroup per CU only (two waves per SIMD: one wave's softmax runs
 // on the vector pipe while the other's products run on the matrix pipe)
 // NADD = addends (0, 1, 2): their prefetched entries are registers.  MINW = waves per SIMD the register budget is held to.
-template <typename T, int DS, int MAXKT, int NW, int NADD, int MINW>
+// CLAMP: `torch.max(scores, torch.tensor(torch.finfo(dtype).min))` between the addends and the softmax (modeling_llama.py:235-236:
+// mask + mask may be -inf in fp16); the other instantiations do not contain the step.
+template <typename T, int DS, int MAXKT, int NW, int NADD, int MINW, bool CLAMP = false>
 __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArgs a) {
     constexpr int DP = 32 * DS, RS = DP * 2 + 16, DT = 2 * DS, NT = 64 * NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -229,6 +232,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArg
                     asm volatile("" : "+v"(t));
                     s = attn_round<T>(t);
                 }
+                if constexpr (CLAMP) s = s != s ? s : fmaxf(s, a.clamp_min);  // torch.maximum: NaN stays NaN; -inf becomes the bound
                 s = 16 * kt + 4 * c + g < Tk ? s : ninf;                      // keys of the padding
                 acc[kt][g] = s;
                 m = fmaxf(m, s);
@@ -321,14 +325,14 @@ static int attn_max_keys(int d) {
     return int(k > 512 ? 512 : k);
 }
 
-template <typename T, int DS, int MAXKT, int NW, int NADD, int MINW> static int attn_launch2(const AttnArgs &a, int64_t bh, hipStream_t s) {
+template <typename T, int DS, int MAXKT, int NW, int NADD, int MINW, bool CLAMP> static int attn_launch2(const AttnArgs &a, int64_t bh, hipStream_t s) {
     constexpr int RS = 32 * DS * 2 + 16;
     const int KT = ((a.Tk + 31) >> 5) << 1;
     const size_t lds = 2 * ((size_t(KT) * 16 * RS + 1023) & ~size_t(1023)) + NW * kAttnScratch;
     static PerDeviceOnce once;
     int dev;
     if (once.needed(&dev)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW, CLAMP>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024) != hipSuccess) {
             set_error("vlmc_attn_fwd: cannot reserve LDS");
             return VLMC_EHIP;
@@ -337,25 +341,25 @@ template <typename T, int DS, int MAXKT, int NW, int NADD, int MINW> static int 
     }
     const dim3 grid{unsigned(bh), unsigned((a.nblk + NW * a.bpw - 1) / (NW * a.bpw))}, block{64 * NW};
     const LaunchEvents ev = take_launch_events();
-    if (ev.start || ev.stop) hipExtLaunchKernelGGL((attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW>), grid, block, lds, s, ev.start, ev.stop, 0, a);
-    else hipLaunchKernelGGL((attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW>), grid, block, lds, s, a);
+    if (ev.start || ev.stop) hipExtLaunchKernelGGL((attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW, CLAMP>), grid, block, lds, s, ev.start, ev.stop, 0, a);
+    else hipLaunchKernelGGL((attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW, CLAMP>), grid, block, lds, s, a);
     return VLMC_OK;
 }
 
-template <typename T, int DS, int NADD> static int attn_launch(const AttnArgs &a, int64_t bh, hipStream_t s) {
+template <typename T, int DS, int NADD, bool CLAMP> static int attn_launch(const AttnArgs &a, int64_t bh, hipStream_t s) {
     const int KT = ((a.Tk + 31) >> 5) << 1;
-    if (KT <= 4) return attn_launch2<T, DS, 4, 4, NADD, 3>(a, bh, s);
-    if (KT <= 8) return attn_launch2<T, DS, 8, 4, NADD, 3>(a, bh, s);
-    if (KT <= 12) return attn_launch2<T, DS, 12, 4, NADD, 2>(a, bh, s);
-    if constexpr (DS == 4) return attn_launch2<T, DS, 18, 4, NADD, 1>(a, bh, s);  // (head_dim 128: at most 288 keys fit, with four waves' scratch)
-    else if (KT <= 18) return attn_launch2<T, DS, 18, 8, NADD, 2>(a, bh, s);
-    else if constexpr (DS == 2) return attn_launch2<T, DS, 32, 8, NADD, 2>(a, bh, s);
-    else return attn_launch2<T, DS, 22, 8, NADD, 2>(a, bh, s);                    // (head_dim 96: at most 352 keys fit)
+    if (KT <= 4) return attn_launch2<T, DS, 4, 4, NADD, 3, CLAMP>(a, bh, s);
+    if (KT <= 8) return attn_launch2<T, DS, 8, 4, NADD, 3, CLAMP>(a, bh, s);
+    if (KT <= 12) return attn_launch2<T, DS, 12, 4, NADD, 2, CLAMP>(a, bh, s);
+    if constexpr (DS == 4) return attn_launch2<T, DS, 18, 4, NADD, 1, CLAMP>(a, bh, s);  // (head_dim 128: at most 288 keys fit, with four waves' scratch)
+    else if (KT <= 18) return attn_launch2<T, DS, 18, 8, NADD, 2, CLAMP>(a, bh, s);
+    else if constexpr (DS == 2) return attn_launch2<T, DS, 32, 8, NADD, 2, CLAMP>(a, bh, s);
+    else return attn_launch2<T, DS, 22, 8, NADD, 2, CLAMP>(a, bh, s);                    // (head_dim 96: at most 352 keys fit)
 }
 
 // one translation unit per (dtype, number of addends): `make -j` compiles them side by side
-template <typename T, int NADD> static int attn_dispatch(const AttnArgs &a, int64_t bh, int ds, hipStream_t s) {
-    return ds <= 2 ? attn_launch<T, 2, NADD>(a, bh, s) : ds == 3 ? attn_launch<T, 3, NADD>(a, bh, s) : attn_launch<T, 4, NADD>(a, bh, s);
+template <typename T, int NADD, bool CLAMP = false> static int attn_dispatch(const AttnArgs &a, int64_t bh, int ds, hipStream_t s) {
+    return ds <= 2 ? attn_launch<T, 2, NADD, CLAMP>(a, bh, s) : ds == 3 ? attn_launch<T, 3, NADD, CLAMP>(a, bh, s) : attn_launch<T, 4, NADD, CLAMP>(a, bh, s);
 }
 int attn_dispatch_f16_0(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
 int attn_dispatch_f16_1(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
@@ -363,5 +367,9 @@ int attn_dispatch_f16_2(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
 int attn_dispatch_bf16_0(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
 int attn_dispatch_bf16_1(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
 int attn_dispatch_bf16_2(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
+int attn_dispatch_clamp_f16_1(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);      // (with the clamp: one or two addends)
+int attn_dispatch_clamp_f16_2(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
+int attn_dispatch_clamp_bf16_1(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
+int attn_dispatch_clamp_bf16_2(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
 
 }  // namespace vlmc

@@ -71,6 +71,11 @@ PAD_MASK_KEYS = {"attention_mask": "self", "encoder_attention_mask": "cross"}
 PAD_STATE_KEYS = {"encoder_hidden_states": "cross"}
 
 
+# integer tensors [1, T_j] that index by token (LlamaModel.forward hands every layer `position_ids`, modeling_llama.py:532-537, and the
+# layer gathers its rotary tables by them, :133-137): padded with 0 behind a sample's own tokens -- a valid index whose rows nobody reads
+PAD_INDEX_KEYS = ("position_ids",)
+
+
 def plan_padded(cur_in, caches, n_samples, group_max):
     """[(chunk, spec)] covering samples 0 .. n_samples - 1 with PADDED groups, or None when the samples are not ragged or cannot be
     padded (no mask kwarg to hide the padding behind, tensors this function does not know how to pad, mixed dtypes / widths)."""
@@ -97,6 +102,9 @@ def plan_padded(cur_in, caches, n_samples, group_max):
                 if v.dim() != 3 or v.shape[0] != 1 or v.shape[2] != v0.shape[2]:
                     return None
                 s_len = v.shape[1]
+            elif k in PAD_INDEX_KEYS:
+                if v.is_floating_point() or v.is_complex() or v.dtype is torch.bool or v.dim() != 2 or v.shape[0] != 1 or v.shape[1] != t:
+                    return None
             elif k not in PAD_MASK_KEYS:
                 return None                                           # a tensor kwarg nobody told us how to pad
         for k, kind in PAD_MASK_KEYS.items():
@@ -192,6 +200,8 @@ def _pad_caches(group, spec):
             out[k] = v0
         elif k in PAD_STATE_KEYS:
             out[k] = _ragged_to_padded([c[k][0] for c in group], sp, 0)
+        elif k in PAD_INDEX_KEYS:
+            out[k] = _ragged_to_padded([c[k][0] for c in group], tp, 0)          # [n, tp]
         else:
             keys = tp if PAD_MASK_KEYS[k] == "self" else sp
             q = tp if v0.shape[2] != 1 else 1

@@ -89,6 +89,8 @@ CROSSCHECK = {
     "VLMC_ROW_SLICES": ("1", "0: a token slice of a padded fp32 stack is multiplied with its padding rows"),
     "VLMC_MEMO_COPY": ("0", "1: what a finished tower remembers of a capture phase is copied instead of kept with its version"),
     "VLMC_TORCH_FUNCTION_MODE": ("0", "1: the replay's routing through a scoped TorchFunctionMode instead of attribute patches"),
+    "VLMC_ATTN_CLAMP": ("1", "0: an attention chain with the LLaMA clamp (torch.max against finfo.min) is computed op by op from the clamp on"),
+    "VLMC_ROPE": ("1", "0: apply_rotary_pos_emb of a LLaMA attention runs as the model file's ~16 launches"),
     "VLMC_GROUP_VIEWS": ("1", "0: a merged forward's group is handed copies of a finished tower's block outputs, not views"),
 }
 

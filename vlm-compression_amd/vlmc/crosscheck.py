@@ -58,6 +58,8 @@ ROUTES = {
     "memo_copies": ({"VLMC_MEMO_COPY": "1"}, "what a finished tower remembers of a capture phase (its block-0 arguments, its outputs) is copied instead of kept with its version"),
     "patches_as_function_mode": ({"VLMC_TORCH_FUNCTION_MODE": "1"}, "the replay's routing of matmul / softmax / gelu / mean / sdpa through a scoped TorchFunctionMode instead of attribute patches"),
     "group_stacks": ({"VLMC_GROUP_VIEWS": "0"}, "a merged forward's group is handed copies (torch.cat) of every block output of a finished tower, not views of the padded pass"),
+    "attn_clamp_unfused": ({"VLMC_ATTN_CLAMP": "0"}, "a LLaMA attention chain (scores / sqrt(d) + mask, torch.max against finfo.min, fp32 softmax) is realized at the clamp: vlmc_attn_matmul, torch elementwise, vlmc_softmax_rows instead of vlmc_attn_fwd_clamp"),
+    "rope_op_sequence": ({"VLMC_ROPE": "0"}, "apply_rotary_pos_emb runs as the model file's gathers, slices, cat and elementwise ops instead of vlmc_rope"),
     "host_ctypes": ({"VLMC_FAST": "0"}, "every launch through the ctypes route (no compiled host path)"),
 }
 

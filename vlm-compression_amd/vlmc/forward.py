@@ -23,6 +23,7 @@ module as before, only `forward` is replaced."""
 from __future__ import annotations
 
 import contextlib
+import sys
 import threading
 import weakref
 
@@ -36,7 +37,7 @@ _active = 0
 stats = {"kernel": 0, "library": 0, "grouped_launches": 0, "served_from_group": 0, "stash_dropped": 0, "attn_kernel": 0,
          "attn_library": 0, "mean_kernel": 0, "sdpa_kernel": 0, "sdpa_library": 0, "norm_kernel": 0, "softmax_kernel": 0,
          "attn_fused": 0, "attn_chain_unfused": 0, "attn_fused_checks": 0, "gelu_kernel": 0, "kernel_rows": 0, "attn_fused_lens": 0,
-         "kernel_slices": 0}
+         "kernel_slices": 0, "attn_fused_clamp": 0, "rope_kernel": 0, "rope_checks": 0}
 
 # first member of a learned sibling group -> tuple of weak references to all members, in call order
 _SIBLINGS = weakref.WeakKeyDictionary()
@@ -424,9 +425,10 @@ class LazyScores(torch.Tensor):
     p32 / p16 probabilities in fp32 / the dtype."""
 
     @staticmethod
-    def __new__(cls, q, kt, shape, dtype, state="s16", ops_=(), mul=None, adds=(), base=None):
+    def __new__(cls, q, kt, shape, dtype, state="s16", ops_=(), mul=None, adds=(), base=None, clamp=None):
         r = torch.Tensor._make_wrapper_subclass(cls, shape, dtype=dtype, device=q.device)
         r._q, r._kt, r._state, r._ops, r._mul, r._adds, r._real = q, kt, state, list(ops_), mul, list(adds), None
+        r._clamp = clamp                                                  # the kernel's clamp_min (a value of the dtype), or None
         r._dt16 = q.dtype if base is None else base
         r._consumed = False
         _LAZY_LIVE.add(r)
@@ -434,7 +436,7 @@ class LazyScores(torch.Tensor):
 
     def _child(self, state, dtype=None):
         return LazyScores(self._q, self._kt, self.shape, self.dtype if dtype is None else dtype, state, self._ops, self._mul, self._adds,
-                          self._dt16)
+                          self._dt16, self._clamp)
 
     def _realize(self):
         """The tensor the model's ops would have produced so far, on the unfused kernels."""
@@ -510,8 +512,8 @@ def _lz_add(func, args, kw, inplace=False):
         pos = (b, _SELF)
     else:
         pos = (_SELF, b)
-    if type(a) is not LazyScores or a._real is not None or a._state != "s16" or len(a._adds) >= 2 or type(b) is not torch.Tensor or \
-            b.dtype != a._dt16 or b.device != a._q.device or b.requires_grad or b.dim() > 4 or b.dim() == 0:
+    if type(a) is not LazyScores or a._real is not None or a._state != "s16" or len(a._adds) >= 2 or a._clamp is not None or \
+            type(b) is not torch.Tensor or b.dtype != a._dt16 or b.device != a._q.device or b.requires_grad or b.dim() > 4 or b.dim() == 0:
         return NotImplemented
     sh = (1,) * (4 - b.dim()) + tuple(b.shape)
     if any(n not in (1, m) for n, m in zip(sh[:3], a.shape[:3])) or sh[3] != a.shape[3] or min(b.stride()) < 0 or (b.stride(-1) < 1 and sh[3] != 1):
@@ -552,6 +554,67 @@ def _lz_mul(func, args, kw):
     if len(args) == 2 and type(args[0]) is not LazyScores:
         return NotImplemented                                          # (number * lazy arrives as __rmul__(lazy, number))
     return _lz_scale(func, args, kw, False)
+
+
+def attn_clamp_enabled():
+    return config.flag("VLMC_ATTN_CLAMP")
+
+
+def _clamp_bound(b, dt16):
+    """The clamp's lower bound as the Python float the kernel takes, or None: a Python number, or a 0-dim CPU tensor that does not
+    require grad (reading it costs no device sync; a device-resident bound would: the chain is realized instead), holding a finite
+    value that IS a value of the 16-bit dtype -- torch casts a 0-dim bound to the tensor's dtype, and a bound that the cast would
+    change is not worth reasoning about."""
+    if type(b) is torch.Tensor:
+        if b.dim() != 0 or b.device.type != "cpu" or b.requires_grad or b.is_complex() or b.dtype is torch.bool:
+            return None
+        v = b.item()
+    elif type(b) in (int, float):
+        v = b
+    else:
+        return None
+    v = float(v)
+    if v != v or v in (float("inf"), float("-inf")) or torch.tensor(v, dtype=dt16).item() != v:
+        return None
+    return v
+
+
+def _lz_clamp_to(a, bound, func, args, kw):
+    """`max(scores, bound)` after the addends (modeling_llama.py:236), in any spelling: recorded, and kept as the kernel's clamp_min."""
+    if type(a) is not LazyScores or a._real is not None or a._state != "s16" or not a._adds or a._clamp is not None or \
+            not attn_clamp_enabled():
+        return NotImplemented
+    v = _clamp_bound(bound, a._dt16)
+    if v is None:
+        return NotImplemented
+    r = a._child("s16")
+    r._ops.append((func, tuple(_SELF if x is a else x for x in args), {k_: (_SELF if x is a else x) for k_, x in kw.items()}))
+    r._clamp = v
+    return r
+
+
+def _lz_max(func, args, kw):
+    """torch.max(x, t) / torch.maximum(x, t) / x.max(t) / x.maximum(t) with a 0-dim tensor t (`torch.max(x, int)` is a reduction)"""
+    if len(args) + len(kw) != 2 or (set(kw) - {"other"}) or not args:
+        return NotImplemented
+    other = args[1] if len(args) == 2 else kw["other"]
+    if type(other) is not torch.Tensor:
+        return NotImplemented
+    return _lz_clamp_to(args[0], other, func, args, kw)
+
+
+def _lz_clamp(func, args, kw):
+    """torch.clamp(x, min=b) / x.clamp(b) / x.clamp(min=b) (no upper bound) / torch.clamp_min(x, b) / x.clamp_min(b)"""
+    if not args or set(kw) - {"min", "max"}:
+        return NotImplemented
+    pos = list(args[1:])
+    if len(pos) > 2 or (pos and "min" in kw) or (len(pos) == 2 and "max" in kw):
+        return NotImplemented
+    lo = pos[0] if pos else kw.get("min")
+    hi = pos[1] if len(pos) == 2 else kw.get("max")
+    if lo is None or hi is not None:
+        return NotImplemented
+    return _lz_clamp_to(args[0], lo, func, args, kw)
 
 
 def _lz_cast(a, dtype, func, args, kw):
@@ -639,7 +702,9 @@ def _lazy_handlers():
          T.__truediv__: _lz_div, T.div: _lz_div, T.true_divide: _lz_div, torch.div: _lz_div, torch.true_divide: _lz_div,
          T.__mul__: _lz_mul, T.__rmul__: _lz_mul, T.mul: _lz_mul, torch.mul: _lz_mul,
          T.float: _lz_float, T.half: _lz_half, T.bfloat16: _lz_bfloat16, T.to: _lz_to, T.type_as: _lz_type_as,
-         F.dropout: _lz_dropout, torch.dropout: _lz_dropout}
+         F.dropout: _lz_dropout, torch.dropout: _lz_dropout,
+         torch.max: _lz_max, torch.maximum: _lz_max, T.max: _lz_max, T.maximum: _lz_max,
+         torch.clamp: _lz_clamp, T.clamp: _lz_clamp, torch.clamp_min: _lz_clamp, T.clamp_min: _lz_clamp}
     for f in (T.size, T.dim, T.numel, T.nelement, T.element_size, T.is_floating_point, T.is_complex, T.get_device, T.ndimension,
               T.is_contiguous, T.stride):
         _LAZY_META_FUNCS.add(f)
@@ -655,7 +720,7 @@ def _chain_signature(a, v):
         sh = (1,) * (4 - t.dim()) + tuple(t.shape)
         return tuple(n != 1 for n in sh[:3])
     return (q.dtype, q.shape[-1], a._mul is not None, tuple(pat(t) for t in a._adds),
-            tuple(f is _SELF or getattr(f, "__name__", "") for f, _a, _k in a._ops))
+            tuple(f is _SELF or getattr(f, "__name__", "") for f, _a, _k in a._ops), a._clamp is not None)
 
 
 def _lazy_matmul(a, b, matmul):
@@ -671,7 +736,8 @@ def _lazy_matmul(a, b, matmul):
             ok = _FUSED_OK.get(sig)
             ql, kl = _pad_lengths(a._q, k, a._adds) if _PAD_LENGTHS is not None else (None, None)
             if ok is None and not torch.cuda.is_current_stream_capturing():
-                fused = ops.attn_fused(a._q, k, b, a._mul, a._adds, plan)
+                fused = ops.attn_fused(a._q, k, b, a._mul, a._adds, plan) if a._clamp is None else \
+                    ops.attn_fused_clamp(a._q, k, b, a._mul, a._adds, a._clamp, plan)
                 ref = matmul(a._realize(), b)
                 ok = _FUSED_OK[sig] = bool(fused.shape == ref.shape and torch.equal(fused.contiguous().view(torch.int16),
                                                                                   ref.contiguous().view(torch.int16)))
@@ -682,11 +748,16 @@ def _lazy_matmul(a, b, matmul):
                                   "this chain stays unfused", RuntimeWarning)
                     return ref
                 stats["attn_fused"] += 1
+                stats["attn_fused_clamp"] += a._clamp is not None
                 a._consumed = True
                 return fused
             if ok:
                 stats["attn_fused"] += 1
                 a._consumed = True
+                if a._clamp is not None:                              # (a chain without a clamp: exactly the calls below)
+                    stats["attn_fused_clamp"] += 1
+                    stats["attn_fused_lens"] += ql is not None or kl is not None
+                    return ops.attn_fused_clamp(a._q, k, b, a._mul, a._adds, a._clamp, plan, ql, kl)
                 if ql is not None or kl is not None:
                     stats["attn_fused_lens"] += 1
                     return ops.attn_fused(a._q, k, b, a._mul, a._adds, plan, ql, kl)
@@ -712,9 +783,12 @@ def _make_matmul(orig):
             if (torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() != a.dtype) or (a.dtype is f32 and not f32_on):
                 return orig(a, b)                                   # (autocast would cast the operands: the library's call)
             if lazy and a.dim() == 4 and b.dim() == 4 and b.stride(2) == 1 and a.stride(3) == 1 and b.shape[3] > 1 and \
-                    a.dtype is b.dtype and a.shape[:2] == b.shape[:2] and ops.attn_fused_plan(a, b.transpose(2, 3), b.transpose(2, 3)) is not None:
-                # q @ k^T of an attention (k^T: a transposed view, keys K-contiguous): answered lazily
-                return LazyScores(a, b, (*a.shape[:3], b.shape[3]), a.dtype)
+                    a.dtype is b.dtype and a.shape[:2] == b.shape[:2]:
+                if ops.attn_fused_plan(a, b.transpose(2, 3), b.transpose(2, 3)) is not None:
+                    # q @ k^T of an attention (k^T: a transposed view, keys K-contiguous): answered lazily
+                    return LazyScores(a, b, (*a.shape[:3], b.shape[3]), a.dtype)
+                if a.dtype in ops._16BIT and a.is_cuda and a.shape[3] % 8 == 0 and 0 < a.shape[3] <= 128 and b.shape[3] > ops.attn_max_keys(a.shape[3]):
+                    stats["attn_chain_unfused"] += 1                  # more keys than a head's K and V may take of LDS: op by op, below
             out = ops.attn_matmul(a, b, None, True)                   # (looked up per call: bench.py's probe wraps it); None: not a
             if out is not None:                                       # product the kernel computes
                 stats["attn_kernel"] += 1
@@ -1009,6 +1083,96 @@ def _make_norm(m, mode, eps):
     return forward
 
 
+# ---- the rotary position embedding of a LLaMA attention: one launch instead of ~16 ---------------------------------------------------
+# The reference's `LlamaAttention.forward` calls the MODULE-LEVEL function `apply_rotary_pos_emb(q, k, cos, sin, position_ids)`
+# (modeling_llama.py:133-140, :212): gathers, slices, a cat and six elementwise ops per operand.  For the duration of a replay that
+# global is replaced by a wrapper that runs `vlmc_rope` -- found by NAME in the module that defines the class of the block's
+# `self_attn`, and replaced only after the original and the kernel have given the same BITS on seeded random operands (strided q / k
+# views, non-monotonic positions, a [1, T] row and a [B, T] matrix), once per (function, dtype, head_dim), outside any graph capture.
+# A model without such a function, or whose function is another computation, keeps its own ops.  `VLMC_ROPE=0`: never.
+_ROPE_NAME = "apply_rotary_pos_emb"
+_ROPE_OK = {}                 # (function, dtype, head_dim) -> True / False
+
+
+def rope_enabled():
+    return config.flag("VLMC_ROPE")
+
+
+def _rope_verdict(fn, dtype, d, device):
+    key = (fn, dtype, d)
+    ok = _ROPE_OK.get(key)
+    if ok is not None:
+        return ok
+    ok = False
+    try:
+        g = torch.Generator(device=device).manual_seed(20241016)
+        B, H, T, P = 3, 5, 37, 61
+        qkv = torch.randn(B, T, 3, H, d, generator=g, device=device).to(dtype)
+        q, k = qkv[:, :, 0].transpose(1, 2), qkv[:, :, 1].transpose(1, 2)
+        cos = (torch.rand(1, 1, P, d, generator=g, device=device) * 2 - 1).to(dtype)
+        sin = (torch.rand(1, 1, P, d, generator=g, device=device) * 2 - 1).to(dtype)
+        ok = True
+        with torch.no_grad():
+            for pos in (torch.randint(0, P, (B, T), generator=g, device=device), torch.randint(0, P, (1, T), generator=g, device=device)):
+                c_, s_ = cos[:, :, :P - 3], sin[:, :, :P - 3]             # (tables cut like `rotary_emb(..)[:, :, :seq_len]`: views)
+                pos = pos.clamp(max=P - 4)
+                plan = ops.rope_supported(q, k, c_, s_, pos)
+                if plan is None:
+                    ok = False
+                    break
+                want = fn(q, k, c_, s_, pos)
+                got = ops.rope(q, k, c_, s_, pos, None, plan)
+                if not (isinstance(want, tuple) and len(want) == 2 and all(
+                        isinstance(w, torch.Tensor) and w.dtype == dtype and w.shape == o.shape and
+                        torch.equal(w.contiguous().view(torch.int16), o.contiguous().view(torch.int16)) for w, o in zip(want, got))):
+                    ok = False
+                    break
+        stats["rope_checks"] += 1
+    except Exception:
+        ok = False
+    _ROPE_OK[key] = ok
+    return ok
+
+
+def _make_rope(orig):
+    def apply_rotary_pos_emb(q, k, cos, sin, position_ids, *a, **kw):
+        if not a and not kw and _ident() == _mm_owner and type(q) is torch.Tensor and type(k) is torch.Tensor and type(cos) is torch.Tensor \
+                and type(sin) is torch.Tensor and type(position_ids) is torch.Tensor and not torch.is_grad_enabled() and q.is_cuda and \
+                _ROPE_OK.get((orig, q.dtype, q.shape[-1])) and not (torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() != q.dtype):
+            plan = ops.rope_supported(q, k, cos, sin, position_ids)
+            if plan is not None:
+                ql = _PAD_LENGTHS.get(q.shape[2]) if _PAD_LENGTHS is not None else None
+                if ql is not None and ql.shape[0] != q.shape[0]:
+                    ql = None
+                stats["rope_kernel"] += 1
+                return ops.rope(q, k, cos, sin, position_ids, ql, plan)
+        return orig(q, k, cos, sin, position_ids, *a, **kw)
+    apply_rotary_pos_emb._vlmc_rope_orig = orig
+    return apply_rotary_pos_emb
+
+
+def _install_ropes(roots):
+    """[(python module, original function)] of the rotary functions replaced for `roots` (restored by the caller)."""
+    import types
+    done = []
+    for root in roots:
+        attn = getattr(root, "self_attn", None)
+        if not isinstance(attn, nn.Module):
+            continue
+        pymod = sys.modules.get(type(attn).__module__)
+        fn = pymod.__dict__.get(_ROPE_NAME) if pymod is not None else None
+        if not isinstance(fn, types.FunctionType) or hasattr(fn, "_vlmc_rope_orig"):
+            continue
+        w = next((p_ for p_ in attn.parameters() if p_.dim() == 2), None)
+        d = getattr(attn, "head_dim", None)
+        if w is None or not w.is_cuda or w.dtype not in ops._16BIT or type(d) is not int or d % 8 or not 0 < d <= 128:
+            continue
+        if _rope_verdict(fn, w.dtype, d, w.device):
+            setattr(pymod, _ROPE_NAME, _make_rope(fn))
+            done.append((pymod, fn, w.device))
+    return done
+
+
 @contextlib.contextmanager
 def invariant_linears(modules, roots=()):
     """Route the forward of the given `nn.Linear` modules (exact type) through `linear` for the duration -- and the batched
@@ -1023,9 +1187,13 @@ def invariant_linears(modules, roots=()):
     for m in patched:
         m.forward = (lambda mod: (lambda x: tracker.call(mod, x)))(m)
     _active += 1
-    norms = []
+    norms, ropes = [], []
+    rope_before = stats["rope_kernel"]
     try:
         with invariant_matmuls():
+            if roots and rope_enabled() and attn_matmul_enabled() and _mm_owner == _ident() and torch.cuda.is_available() \
+                    and not torch.cuda.is_current_stream_capturing():
+                ropes = _install_ropes(roots)
             if roots and rms_norm_enabled() and attn_matmul_enabled() and config.flag("VLMC_ROW_MEAN") \
                     and torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
                 for root in roots:
@@ -1045,3 +1213,8 @@ def invariant_linears(modules, roots=()):
             m.__dict__.pop("forward", None)
         for m in norms:
             m.__dict__.pop("forward", None)
+        for pymod, fn, _dev in ropes:
+            setattr(pymod, _ROPE_NAME, fn)
+        if ropes and stats["rope_kernel"] != rope_before and sys.exc_info()[0] is None and not torch.cuda.is_current_stream_capturing():
+            for dev in {d_ for _m, _f, d_ in ropes}:
+                ops.rope_check(dev)                                  # a position outside the cos / sin table: raised here, never read

@@ -502,6 +502,14 @@ _I64x3 = ctypes.c_int64 * 3
 _I64x4 = ctypes.c_int64 * 4
 
 
+def attn_max_keys(d: int) -> int:
+    """keys a head may have in `attn_fused` for head_dim d (a head's K and V live in LDS: vlmc_attn_max_keys)"""
+    mk = _attn_max_keys.get(d)
+    if mk is None:
+        mk = _attn_max_keys[d] = int(_lib.load().vlmc_attn_max_keys(d))
+    return mk
+
+
 def attn_fused_plan(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, adds=(), _cuda_only: bool = True):
     """(B, H, Tq, Tk, d) if `vlmc_attn_fwd` computes the reference-op attention chain for these operands, else None: q [B, H, Tq, d],
     k, v [B, H, Tk, d] CUDA tensors of one 16-bit dtype with unit stride along d (k is the operand BEFORE its transpose), d a multiple
@@ -518,10 +526,7 @@ def attn_fused_plan(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, adds=(), 
         st = t.stride()
         if (st[3] != 1 and d != 1) or min(st[0], st[1], st[2]) < 0:
             return None
-    mk = _attn_max_keys.get(d)
-    if mk is None:
-        mk = _attn_max_keys[d] = int(_lib.load().vlmc_attn_max_keys(d))
-    if Tk > mk or len(adds) > 2:
+    if Tk > attn_max_keys(d) or len(adds) > 2:
         return None
     for t in adds:
         if t.dtype != q.dtype or t.device != q.device or t.dim() > 4 or t.dim() == 0 or t.requires_grad:
@@ -546,6 +551,20 @@ def attn_fused(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mul=None, adds
     tensor (the model's `.transpose(1, 2).reshape(B, Tq, H * d)` is free).  `mul`: a Python float already rounded to fp32.
     `q_len` / `k_len` (int32 device tensors [B], a padded group of ragged samples): output rows behind q_len[b] are zeros; keys
     behind k_len[b] -- which an addend must mask -- are skipped (include/vlmc.h: vlmc_attn_fwd_lens)."""
+    return _attn_fused(q, k, v, mul, adds, _plan, q_len, k_len, None)
+
+
+def attn_fused_clamp(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mul=None, adds=(), clamp_min: float = 0.0, _plan=None, q_len=None,
+                     k_len=None) -> torch.Tensor:
+    """`attn_fused` with the clamp of the reference's LLaMA attention between the addends and the softmax (modeling_llama.py:235-236:
+    `s = torch.max(s, torch.tensor(torch.finfo(s.dtype).min))`; include/vlmc.h: vlmc_attn_fwd_clamp).  `clamp_min`: a finite Python
+    float that IS a value of the dtype; one or two addends."""
+    if not adds:
+        raise ValueError("vlmc.attn_fused_clamp: the clamp follows an addend")
+    return _attn_fused(q, k, v, mul, adds, _plan, q_len, k_len, float(clamp_min))
+
+
+def _attn_fused(q, k, v, mul, adds, _plan, q_len, k_len, clamp_min):
     _need_gpu(q, k, v, q_len, k_len)
     plan = _plan if _plan is not None else attn_fused_plan(q, k, v, adds)
     if plan is None:
@@ -560,13 +579,79 @@ def attn_fused(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mul=None, adds
             raise TypeError("vlmc.attn_fused: q_len / k_len must be contiguous int32 [batch] tensors")
     if k_len is not None and a0 is None:
         raise ValueError("vlmc.attn_fused: k_len needs an addend that masks the keys behind it")
-    _lib.check(_lib.load().vlmc_attn_fwd_lens(
-        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _DT[q.dtype], B, H, Tq, Tk, d, _I64x3(*q.stride()[:3]),
-        _I64x3(*k.stride()[:3]), _I64x3(*v.stride()[:3]), 0 if mul is None else 1, 0.0 if mul is None else float(mul),
-        None if a0 is None else a0.data_ptr(), None if a0 is None else _add_strides(a0, B, H, Tq),
-        None if a1 is None else a1.data_ptr(), None if a1 is None else _add_strides(a1, B, H, Tq),
-        None if q_len is None else q_len.data_ptr(), None if k_len is None else k_len.data_ptr(), _stream()))
+    head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _DT[q.dtype], B, H, Tq, Tk, d, _I64x3(*q.stride()[:3]),
+            _I64x3(*k.stride()[:3]), _I64x3(*v.stride()[:3]), 0 if mul is None else 1, 0.0 if mul is None else float(mul),
+            None if a0 is None else a0.data_ptr(), None if a0 is None else _add_strides(a0, B, H, Tq),
+            None if a1 is None else a1.data_ptr(), None if a1 is None else _add_strides(a1, B, H, Tq))
+    lens = (None if q_len is None else q_len.data_ptr(), None if k_len is None else k_len.data_ptr(), _stream())
+    if clamp_min is None:
+        _lib.check(_lib.load().vlmc_attn_fwd_lens(*head, *lens))
+    else:
+        _lib.check(_lib.load().vlmc_attn_fwd_clamp(*head, clamp_min, *lens))
     return out.permute(0, 2, 1, 3)
+
+
+_rope_status = {}             # device index -> int32 [1]: bit 0 set by vlmc_rope when a position lay outside the table
+
+
+def rope_supported(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, position_ids: torch.Tensor, _cuda_only: bool = True):
+    """(B, H, T, d, positions) if `vlmc_rope` computes `apply_rotary_pos_emb(q, k, cos, sin, position_ids)` (modeling_llama.py:133-140)
+    for these operands, else None: q, k [B, H, T, d] of one 16-bit dtype with unit stride along d, d a multiple of 8 up to 128; cos, sin
+    [1, 1, positions, d] of the same dtype with unit stride along d; position_ids int64 [B, T] or [1, T]."""
+    if q.dim() != 4 or k.shape != q.shape or q.dtype not in _16BIT or k.dtype != q.dtype or cos.dtype != q.dtype or sin.dtype != q.dtype or \
+            position_ids.dtype != torch.int64 or position_ids.dim() != 2 or (_cuda_only and not all(t.is_cuda for t in (q, k, cos, sin, position_ids))):
+        return None
+    B, H, T, d = q.shape
+    if d % 8 or d > 128 or min(B, H, T, d) <= 0 or q.stride(3) != 1 or k.stride(3) != 1 or min(q.stride()) < 0 or min(k.stride()) < 0:
+        return None
+    if cos.dim() != 4 or cos.shape[:2] != (1, 1) or cos.shape[3] != d or sin.shape != cos.shape or cos.stride(3) != 1 or sin.stride(3) != 1 or \
+            cos.stride(2) != sin.stride(2) or cos.stride(2) < d or cos.shape[2] < 1:
+        return None
+    if position_ids.shape[1] != T or position_ids.shape[0] not in (1, B) or min(position_ids.stride()) < 0:
+        return None
+    if any(t.device != q.device for t in (k, cos, sin, position_ids)) or q.requires_grad or k.requires_grad:
+        return None
+    return B, H, T, d, cos.shape[2]
+
+
+def rope(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, position_ids: torch.Tensor, q_len=None, _plan=None):
+    """`apply_rotary_pos_emb(q, k, cos, sin, position_ids)` of the reference's LLaMA attention (modeling_llama.py:126-140) for q and k in
+    one launch (include/vlmc.h: vlmc_rope): `wd(wd(x * cos[p]) + wd(rotate_half(x) * sin[p]))`, the bits of the tensor-op sequence.
+    Returns (q_embed, k_embed) as [B, H, T, d] views of contiguous [B, T, H, d] tensors -- the memory order torch's own elementwise ops
+    give the transposed views of the q / k linears, and what `attn_fused*` reads in place.  `q_len` (int32 device tensor [B]): rows behind
+    a sample's length are not read and come out as zeros.  A position outside the table is never read; `rope_check()` raises for it."""
+    _need_gpu(q, k, cos, sin, position_ids, q_len)
+    plan = _plan if _plan is not None else rope_supported(q, k, cos, sin, position_ids)
+    if plan is None:
+        raise TypeError("vlmc.rope: q, k [B, H, T, d] of one 16-bit dtype with unit stride along d (d a multiple of 8 up to 128), cos / sin "
+                        "[1, 1, positions, d] of that dtype and int64 position_ids [B, T] or [1, T] expected")
+    B, H, T, d, positions = plan
+    if q_len is not None and (q_len.dtype != torch.int32 or q_len.shape != (B,) or not q_len.is_contiguous()):
+        raise TypeError("vlmc.rope: q_len must be a contiguous int32 [batch] tensor")
+    qo = torch.empty((B, T, H, d), dtype=q.dtype, device=q.device)
+    ko = torch.empty((B, T, H, d), dtype=q.dtype, device=q.device)
+    dev = q.device.index if q.device.index is not None else torch.cuda.current_device()
+    st = _rope_status.get(dev)
+    if st is None:
+        st = _rope_status[dev] = torch.zeros(1, dtype=torch.int32, device=q.device)
+    _lib.check(_lib.load().vlmc_rope(
+        q.data_ptr(), k.data_ptr(), qo.data_ptr(), ko.data_ptr(), _DT[q.dtype], B, H, T, d, _I64x3(*q.stride()[:3]), _I64x3(*k.stride()[:3]),
+        _I64x3(T * H * d, d, H * d), cos.data_ptr(), sin.data_ptr(), positions, cos.stride(2), position_ids.data_ptr(),
+        0 if position_ids.shape[0] == 1 else position_ids.stride(0), position_ids.stride(1), None if q_len is None else q_len.data_ptr(),
+        st.data_ptr(), _stream()))
+    return qo.permute(0, 2, 1, 3), ko.permute(0, 2, 1, 3)
+
+
+def rope_check(device=None):
+    """Raise if a `rope` call on `device` since the last check was handed a position outside its table (synchronises the stream)."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    st = _rope_status.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    if st is None:
+        return
+    rc = _lib.load().vlmc_rope_status(st.data_ptr(), _stream())
+    if rc:
+        st.zero_()
+    _lib.check(rc)
 
 
 def pack_24(weight: torch.Tensor, mask: torch.Tensor):
