@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VLMC_ABI_VERSION 22
+#define VLMC_ABI_VERSION 23
 
 #define VLMC_OK 0
 #define VLMC_EINVAL (-1)     /* bad argument (shape, dtype, alignment, null pointer) */
@@ -440,6 +440,17 @@ int vlmc_rms_norm(const void *x, int dtype, int64_t rows, int64_t n, int64_t ldx
 size_t vlmc_hessian_workspace(int dtype, int64_t rows, int64_t in_features);
 int vlmc_hessian_accum(const void *X, int dtype, int64_t rows, int64_t in_features, int64_t ldx, float *H, int64_t ldh,
                        float alpha, float beta, void *workspace, size_t workspace_bytes, void *stream);
+/* vlmc_hessian_accum_rows: the same update over the rows of X that a row map names -- add_batch (sparsegpt_pruner.py:68-79) for ONE
+ * padded forward of ragged calibration samples, whose X [rows_total, in_features] holds every sample's own token rows followed by padding rows
+ * of unspecified content.  H = alpha * H + beta * Xr^T Xr with Xr = rows row_map[0 .. n_rows) of X, in that order (row_map: device int32, as
+ * the replay's row maps are built: the flattened indices of the real rows first; NULL = the identity).  The rows are gathered while the
+ * operand is transposed into the workspace, so the product's extent is n_rows, vlmc_hessian_workspace(dtype, n_rows, in_features) bytes
+ * suffice and no other row of X is read; the result has the bits of vlmc_hessian_accum on those rows as a contiguous [n_rows, in_features]
+ * matrix, for all three dtypes.  A map entry outside [0, rows_total) contributes a zero row.  VLMC_EINVAL unless 0 < n_rows <= rows_total
+ * < 2^24 and in_features <= 16 * 65535 (what the launch grids hold). */
+int vlmc_hessian_accum_rows(const void *X, int dtype, int64_t rows_total, int64_t in_features, int64_t ldx, const int32_t *row_map,
+                            int64_t n_rows, float *H, int64_t ldh, float alpha, float beta, void *workspace, size_t workspace_bytes,
+                            void *stream);
 int vlmc_symmetrize_lower(float *H, int64_t n, int64_t ldh, void *stream);
 
 /* ---- K9: diagonal block of the blocked Cholesky factorization ------------------------------
@@ -526,10 +537,16 @@ int vlmc_sparsegpt_prune_blocks(float *W, int64_t out_features, int64_t in_featu
  * vlmc_act_moments: per hook call and channel (layout as vlmc_act_sqnorm) the squared norm, the
  *   plain sum over tokens and the population variance -- the three per-call quantities of the DSnoT
  *   `WrappedGPT.add_batch` (dsnot_pruner.py:79-101).  Any output pointer may be NULL.
+ * vlmc_act_moments_lens: the same for the calls of ONE padded forward of ragged calibration samples (:79-101 once per sample): call c
+ *   owns its first min(call_tokens[c], tokens) token rows (call_tokens: device int32 [n_calls]; NULL = vlmc_act_moments); only those are
+ *   read, the variance divides by their number, and call c's three outputs have the bits of vlmc_act_moments on that sample alone.  A
+ *   count below 1 writes zeros (callers reject it: they know the lengths).
  * vlmc_dsnot_stats_update: the three running means in call order (:92-101); tokens_per_call is a
  *   device array (calls may have different token counts); also emits sqrt(scaler_row) if asked.  */
 int vlmc_act_moments(const void *x, int dtype, int64_t n_calls, int64_t tokens, int64_t in_features, int64_t row_stride,
                      int64_t call_stride, float *normsq, float *sums, float *vars, void *stream);
+int vlmc_act_moments_lens(const void *x, int dtype, int64_t n_calls, int64_t tokens, int64_t in_features, int64_t row_stride,
+                          int64_t call_stride, const int32_t *call_tokens, float *normsq, float *sums, float *vars, void *stream);
 int vlmc_dsnot_stats_update(float *scaler_row, float *sum_row, float *var_row, int64_t in_features, int64_t nsamples_before,
                             int64_t ntokens_before, const float *normsq, const float *sums, const float *vars,
                             const int64_t *tokens_per_call, int64_t n_calls, int64_t batch, float *sqrt_out, void *stream);

@@ -1,4 +1,4 @@
-"""Whole `blipt5_wanda_pruner` / `blipt5_dsnot_pruner` prunes of the REFERENCE-OP InstructBLIP-Vicuna-7B stand-in
+"""Whole `blipt5_wanda_pruner` / `blipt5_dsnot_pruner` / `blipt5_sparsegpt_pruner` prunes of the REFERENCE-OP InstructBLIP-Vicuna-7B stand-in
 (`vlmc.synthetic_llama.InstructBlipVicunaOps`: ViT-g + 32 layers 4096 / 11008 written as modeling_llama.py writes them, fp16; 128
 ragged samples from `calibration_batches(ragged=True, vocab=32000)`: 32 query tokens + 8..128 prompt + 4..16 answer tokens, at most
 176 keys), three legs in ONE command:
@@ -14,7 +14,11 @@ b1 and b2 is the spread the comparison of (c) with (b) is read against.  Every p
 synchronise (`synthetic.time_prune`).  Masks (the zero pattern of every pruned linear, packed) are compared bit for bit: (a) against
 (c) in the child, (b) against (c) through a file under `--scratch`; the number of differing bits is printed.
 
-    python tools/bench_vicuna_ops.py --parent /path/to/parent_tree [--steps 2] [--samples 128] [--methods wanda,dsnot]
+    python tools/bench_vicuna_ops.py --parent /path/to/parent_tree [--steps 2] [--samples 128] [--methods wanda,dsnot,sparsegpt] [--equal-lengths]
+
+`--skip-loop`: without leg (a), so that (c) has its process to itself as (b) has (a whole SparseGPT prune sample by sample leaves the
+allocator in another state than it found it: measured, profiles/ragged_dsnot_sparsegpt.md).  `--equal-lengths`: the same legs on text of ONE length (32 prompt + 16 answer tokens), where nothing is padded: what a change to the ragged
+routes must leave as it was.
 
 Kernel statistics come from a separate run under a tracer (`--child this --legs c --steps 1` after `rocprofv3 --kernel-trace --stats --`):
 tracing and timing never share a run."""
@@ -41,6 +45,8 @@ ap.add_argument("--tree", default=ROOT)
 ap.add_argument("--legs", default="")
 ap.add_argument("--tag", default="")
 ap.add_argument("--child-timeout", type=int, default=900)
+ap.add_argument("--skip-loop", action="store_true", help="leave leg (a) out: (c) then runs alone in its process, as (b) does in its own")
+ap.add_argument("--equal-lengths", action="store_true", help="calibration text of one length instead of the ragged set")
 args = ap.parse_args()
 METHODS = [m for m in args.methods.split(",") if m]
 
@@ -56,7 +62,7 @@ def child():
     torch.manual_seed(0)                                                   # (the linears' biases keep their default initialisation: the same in every process)
     with dev:                                                              # (7 B parameters: initialised where they will live)
         model = synthetic_llama.InstructBlipVicunaOps().eval()
-    batches = synthetic.calibration_batches(args.samples, dev, vocab=32000, ragged=True)
+    batches = synthetic.calibration_batches(args.samples, dev, vocab=32000, ragged=not args.equal_lengths)
     keys = [32 + b["text_input"].shape[1] + b["text_output"].shape[1] for b in batches]
     weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=dev)
 
@@ -118,7 +124,7 @@ def child():
 
 def run_child(which, tree, legs, tag):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", which, "--tree", tree, "--legs", legs, "--tag", tag, "--steps", str(args.steps),
-           "--samples", str(args.samples), "--methods", args.methods, "--scratch", args.scratch]
+           "--samples", str(args.samples), "--methods", args.methods, "--scratch", args.scratch] + (["--equal-lengths"] if args.equal_lengths else [])
     t0 = time.perf_counter()
     p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=args.child_timeout)       # (progress goes to stderr as it happens)
     if p.returncode != 0:
@@ -133,17 +139,17 @@ def main():
     if not args.parent or not os.path.exists(os.path.join(args.parent, "vlm-compression_amd", "vlmc", "synthetic_llama.py")):
         raise SystemExit("--parent: a built checkout of the parent commit with vlmc/synthetic_llama.py copied in")
     b1 = run_child("parent", args.parent, "b", "b1")
-    ac = run_child("this", ROOT, "a,c", "ac")
+    ac = run_child("this", ROOT, "c" if args.skip_loop else "a,c", "ac")
     b2 = run_child("parent", args.parent, "b", "b2")
     shutil.rmtree(args.scratch, ignore_errors=True)
     med = lambda v: sorted(v)[len(v) // 2]
-    print(f"\n{args.samples} ragged samples, keys per sample: mean {ac['keys_mean']:.0f}, max {ac['keys_max']}; {args.steps} timed prunes per leg "
+    print(f"\n{args.samples} {'equal-length' if args.equal_lengths else 'ragged'} samples, keys per sample: mean {ac['keys_mean']:.0f}, max {ac['keys_max']}; {args.steps} timed prunes per leg "
           f"after one warm-up\n")
     print("| method | leg | seconds per prune (each run) | median |")
     print("|---|---|---|---|")
     summary = {}
     for method in METHODS:
-        rows = [("(a) per-sample loop, this build", ac["legs"][f"a/{method}"]["seconds"]),
+        rows = [("(a) per-sample loop, this build", ac["legs"].get(f"a/{method}", {"seconds": [float("nan")]})["seconds"]),
                 ("(b) parent commit, first process", b1["legs"][f"b/{method}"]["seconds"]),
                 ("(b) parent commit, second process", b2["legs"][f"b/{method}"]["seconds"]),
                 ("(c) this build", ac["legs"][f"c/{method}"]["seconds"])]
@@ -156,7 +162,8 @@ def main():
     print()
     for method, s in summary.items():
         print(f"{method}: (c) {s['c']:.3f} s against (b) {s['b']:.3f} s (spread of (b) over both processes {s['b_spread']:.3f} s), (a) {s['a']:.3f} s; "
-              f"mask bits differing of {s['mask_bits']}: (a) vs (c) {s['diff_a_c']}, (b) vs (c) {s['diff_b_c']}")
+              f"mask bits differing of {s['mask_bits']}: (a) vs (c) {s['diff_a_c']}, (b) vs (c) {s['diff_b_c']}"
+              + (" -- informational: SparseGPT's Hessian sums in another order per grouping, by design" if method == "sparsegpt" else ""))
     print("\nforward.stats per prune, (c):", json.dumps({m: ac["legs"][f"c/{m}"]["forward_stats"] for m in METHODS}))
     print("forward.stats per prune, (b):", json.dumps({m: b1["legs"][f"b/{m}"]["forward_stats"] for m in METHODS}))
     print("SUMMARY " + json.dumps(summary))

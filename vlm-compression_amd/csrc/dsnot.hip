@@ -33,13 +33,28 @@ namespace vlmc {
 // sums of x and x^2 (full-rate on CDNA, no division per token), which agrees with torch.var to ~1e-12 relative --
 // the reference's own reduction order is not reproducible to the bit anyway (tests: rtol 2e-6).
 // HBM-bound streaming: 16 tokens in flight per lane through non-temporal loads.
+// `call_tokens` (vlmc_act_moments_lens; NULL = every call has `tokens` rows): call c owns its first min(call_tokens[c], tokens)
+// token rows -- a padded group of ragged samples.  The chains below simply end there, so a call's outputs are the bits of a launch over
+// that sample alone, and the rows behind it are never loaded (the replay leaves them unspecified).  A count below 1 writes zeros.
 template <typename T>
 __global__ __launch_bounds__(64) void act_moments_kernel(const typename T::raw *__restrict__ x, int64_t tokens, int64_t in_f,
                                                          int64_t row_stride, int64_t call_stride, float *__restrict__ normsq,
-                                                         float *__restrict__ sums, float *__restrict__ vars) {
+                                                         float *__restrict__ sums, float *__restrict__ vars,
+                                                         const int32_t *__restrict__ call_tokens = nullptr) {
     const int64_t ch = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (ch >= in_f) return;
     const int64_t call = blockIdx.y;
+    if (call_tokens) {
+        const int64_t own = call_tokens[call];
+        tokens = own < tokens ? own : tokens;
+        if (tokens < 1) {                                         // (the host wrapper rejects it; no division by zero here either)
+            const int64_t o = call * in_f + ch;
+            if (normsq) normsq[o] = 0.f;
+            if (sums) sums[o] = 0.f;
+            if (vars) vars[o] = 0.f;
+            return;
+        }
+    }
     const typename T::raw *p = x + call * call_stride + ch;
     float sq = 0.f, s = 0.f;
     double s1 = 0.0, s2 = 0.0;
@@ -547,26 +562,41 @@ int dsnot_refine_lists(const void *W, int dtype, int64_t out_f, int64_t in_f, in
 }
 using namespace vlmc;
 
-extern "C" int vlmc_act_moments(const void *x, int dtype, int64_t n_calls, int64_t tokens, int64_t in_features,
-                                int64_t row_stride, int64_t call_stride, float *normsq, float *sums, float *vars, void *stream) {
-    VLMC_REQUIRE(x && (normsq || sums || vars), "vlmc_act_moments: null pointer");
+static int act_moments_launch(const char *what, const void *x, int dtype, int64_t n_calls, int64_t tokens, int64_t in_features,
+                              int64_t row_stride, int64_t call_stride, const int32_t *call_tokens, float *normsq, float *sums,
+                              float *vars, void *stream) {
+    VLMC_REQUIRE(x && (normsq || sums || vars), "%s: null pointer", what);
     VLMC_REQUIRE(n_calls >= 0 && n_calls <= 65535 && tokens > 0 && in_features > 0 && row_stride >= in_features,
-                 "vlmc_act_moments: bad shape calls=%lld tokens=%lld in=%lld", (long long)n_calls, (long long)tokens,
+                 "%s: bad shape calls=%lld tokens=%lld in=%lld", what, (long long)n_calls, (long long)tokens,
                  (long long)in_features);
     if (n_calls == 0) return VLMC_OK;
     const dim3 grid(unsigned((in_features + 63) / 64), unsigned(n_calls));
     hipStream_t st = as_stream(stream);
 #define VLMC_MOM(T) hipLaunchKernelGGL((act_moments_kernel<T>), grid, dim3(64), 0, st, static_cast<const T::raw *>(x), tokens, \
-                                       in_features, row_stride, call_stride, normsq, sums, vars)
+                                       in_features, row_stride, call_stride, normsq, sums, vars, call_tokens)
     switch (dtype) {
         case VLMC_F32: VLMC_MOM(f32_t); break;
         case VLMC_F16: VLMC_MOM(f16_t); break;
         case VLMC_BF16: VLMC_MOM(bf16_t); break;
-        default: set_error("vlmc_act_moments: unknown dtype %d", dtype); return VLMC_EINVAL;
+        default: set_error("%s: unknown dtype %d", what, dtype); return VLMC_EINVAL;
     }
 #undef VLMC_MOM
-    VLMC_HIP_CHECK_LAUNCH("vlmc_act_moments");
+    VLMC_HIP_CHECK_LAUNCH(what);
     return VLMC_OK;
+}
+
+extern "C" int vlmc_act_moments(const void *x, int dtype, int64_t n_calls, int64_t tokens, int64_t in_features,
+                                int64_t row_stride, int64_t call_stride, float *normsq, float *sums, float *vars, void *stream) {
+    return act_moments_launch("vlmc_act_moments", x, dtype, n_calls, tokens, in_features, row_stride, call_stride, nullptr, normsq, sums,
+                              vars, stream);
+}
+
+extern "C" int vlmc_act_moments_lens(const void *x, int dtype, int64_t n_calls, int64_t tokens, int64_t in_features,
+                                     int64_t row_stride, int64_t call_stride, const int32_t *call_tokens, float *normsq, float *sums,
+                                     float *vars, void *stream) {
+    // (the launcher bounds what the grid holds: n_calls <= 65535 in y, ceil(in_features / 64) workgroups in x)
+    return act_moments_launch("vlmc_act_moments_lens", x, dtype, n_calls, tokens, in_features, row_stride, call_stride, call_tokens, normsq,
+                              sums, vars, stream);
 }
 
 extern "C" int vlmc_dsnot_stats_update(float *scaler_row, float *sum_row, float *var_row, int64_t in_features,

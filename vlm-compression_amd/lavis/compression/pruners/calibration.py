@@ -78,7 +78,11 @@ from lavis.compression.pruners.replay_padding import (  # noqa: F401
     plan_groups,
     plan_padded,
     row_map,
+    add_batch_rows,
+    in_padded_group,
+    stacked_host_lengths,
     stacked_lengths,
+    stacked_row_map,
     stacked_samples,
 )
 from lavis.compression.pruners.replay_towers import (  # noqa: F401
@@ -377,7 +381,7 @@ def walk_blocks(model, inps, outs, caches, module_to_process, n_samples, autocas
                     kw = stacked_kwargs.get(key)
                     if kw is None:
                         kw = stacked_kwargs[key] = _pad_caches([caches[j] for j in chunk], spec)
-                    _CTX.stacked, _CTX.stacked_lengths = (len(chunk), 1, key), spec["lengths"]
+                    _CTX.stacked, _CTX.stacked_lengths, _CTX.stacked_spec = (len(chunk), 1, key), spec["lengths"], spec
                     graph_stats["padded_forwards"] = graph_stats.get("padded_forwards", 0) + 1
                     try:
                         with forward.padded_rows(spec.get("rows"), spec["lengths"]):     # linears and attention skip the padding rows
@@ -385,7 +389,7 @@ def walk_blocks(model, inps, outs, caches, module_to_process, n_samples, autocas
                     except _TailStop:
                         continue
                     finally:
-                        _CTX.stacked = _CTX.stacked_lengths = None
+                        _CTX.stacked = _CTX.stacked_lengths = _CTX.stacked_spec = None
                     if so is not None:
                         so.end_forward(True)
                     y = y[0] if tuple_output else y

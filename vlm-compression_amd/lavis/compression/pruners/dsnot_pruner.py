@@ -75,7 +75,16 @@ class DsnotStatCollector:
                 stacked = cal.stacked_samples()              # batched replay: one record per stacked calibration sample
                 calls, _b0, idx = stacked if stacked and stacked[0] * stacked[1] == x.shape[0] else (1, x.shape[0], (self._cur,))
                 st = self._dsnot.DsnotInputStat(x.shape[-1], x.device)
-                st.add_calls(x, calls, idx)                  # ONE launch: sum of squares, sum, variance over tokens, per sample
+                # a padded group of ragged samples: the token rows of sample c that are its own (the rest is padding, never read);
+                # the cross-attention's k / v see the ENCODER's padded length: the lookup is by this input's own token dimension
+                lens = cal.stacked_lengths(x.shape[1]) if calls > 1 else None
+                if lens is None and cal.in_padded_group():
+                    raise RuntimeError(f"{name}: a linear input of shape {tuple(x.shape)} inside a padded group of ragged samples "
+                                       "carries no per-sample token counts (VLMC_DSNOT_PAD=0 forwards groups of equal shape)")
+                if lens is None:
+                    st.add_calls(x, calls, idx)              # ONE launch: sum of squares, sum, variance over tokens, per sample
+                else:
+                    st.add_calls(x, calls, idx, call_tokens=lens, host_tokens=cal.stacked_host_lengths(x.shape[1]))
                 hit = (x, st)                                # `x` stays referenced until the next sample (see wanda collector)
                 self._cache[key] = hit
             self.calls[name].append(hit[1])
@@ -92,13 +101,13 @@ class DsnotStatCollector:
             acc = self._fed.get(key)
             if acc is None:
                 acc = sparsegpt.SparseGPT(self.subset[name])
-                acc.add_batch(x, None)
+                cal.add_batch_rows(acc, name, x)
                 self._fed[key] = acc
             self.hessians[name] = acc
         elif self._fed.get(key) is not acc:
             if key in self._fed:
                 raise RuntimeError(f"{name}: the linears sharing an input changed between calibration samples")
-            acc.add_batch(x, None)
+            cal.add_batch_rows(acc, name, x)
             self._fed[key] = acc
         acc._keep_alive = x                                   # the signature holds only while `x` lives
 
@@ -267,7 +276,8 @@ class T5LayerDSnoTPruner(LayerWiseBasePruner, _DsnotBlockMixin):
                               model_prefix=model_prefix, sparsity_ratio=sparsity_ratio, lora_model=lora_model)
 
         cal.walk_blocks(model, inps, outs, caches, module_to_process, n_samples,
-                        lambda: model.maybe_autocast(dtype=torch.bfloat16), prune_block, tuple_output=True)
+                        lambda: model.maybe_autocast(dtype=torch.bfloat16), prune_block, tuple_output=True,
+                        pad_ragged=config.flag("VLMC_DSNOT_PAD"))    # (the statistic takes per-sample token counts, the Hessian a row map)
         cfg.use_cache = use_cache
         cal.release_tower_memory()
         return model

@@ -56,6 +56,41 @@ def stacked_lengths(padded_tokens):
     return None if ln is None else ln.get(int(padded_tokens))
 
 
+def stacked_host_lengths(padded_tokens):
+    """The same counts as `stacked_lengths(padded_tokens)` as a host list (the group's plan has them: nothing is read back from the
+    device), or None."""
+    sp = _CTX.stacked_spec
+    if sp is None:
+        return None
+    if int(padded_tokens) == sp["tp"]:
+        return sp["T"]
+    return sp["S"] if sp["sp"] is not None and int(padded_tokens) == sp["sp"] else None
+
+
+def stacked_row_map(samples, padded_tokens):
+    """During the forward of a PADDED group: (int32 device row map, number of real rows) of a hook input [samples, padded_tokens, d]
+    (`row_map` below: the flattened indices of the samples' own token rows come first), or None."""
+    sp = _CTX.stacked_spec
+    return None if sp is None else sp["rows"].get((int(samples), int(padded_tokens)))
+
+
+def add_batch_rows(acc, name, x):
+    """One Hessian hook call of a SparseGPT accumulator: `acc.add_batch(x, None)` as ever; inside a padded group, with the group's row
+    map for this input, so that only the samples' own token rows enter X^T X.  An input the group has no map for is refused."""
+    if _CTX.stacked_spec is None:
+        return acc.add_batch(x, None)
+    rows = stacked_row_map(x.shape[0], x.shape[1]) if x.dim() == 3 else None
+    if rows is None:
+        raise RuntimeError(f"{name}: a linear input of shape {tuple(x.shape)} inside a padded group of ragged samples has no row map")
+    return acc.add_batch(x, None, rows=rows)
+
+
+def in_padded_group():
+    """Whether the block forward under way is a padded group of ragged samples (a statistics hook that finds no lengths for its input
+    then has to refuse it: it cannot tell the padding rows)."""
+    return _CTX.stacked_spec is not None
+
+
 # ---- ragged calibration text: ONE padded forward per block instead of one per distinct length ---------------------------------
 # Real calibration prompts and answers are ragged (blip2_t5_instruct.py:49-53: up to 128 / 256 tokens); grouping the samples by
 # shape makes 7 / 18 groups per encoder / decoder block pass on the bench's ragged set, each a walk of the block's Python.  A

@@ -97,6 +97,7 @@ class _PruneContext(threading.local):
       capture_sample  index (within this rank's share) of the calibration forward capture_block_inputs is running
       stacked         (samples, batch per sample, sample indices) of the grouped block forward under way (stacked_samples())
       stacked_lengths {padded token count: int32 device tensor [samples]} of a PADDED group of ragged samples, or None
+      stacked_spec    that group's whole plan (replay_padding.plan_padded: host token counts "T" / "S", row maps "rows"), or None
       capture_side    device -> the side stream graphs are captured on
       stream_set      the caller's stream and the capture side streams of the running capture phase"""
 
@@ -106,6 +107,7 @@ class _PruneContext(threading.local):
         self.capture_sample = None
         self.stacked = None
         self.stacked_lengths = None
+        self.stacked_spec = None
         self.capture_group = None          # merged capture: the samples (indices) of the calibration forward that is running
         self.group_defer = False           # .. and finished towers are left for ONE (padded) stacked pass over all groups (ragged batches)
         self.keep_ready = False            # .. and a tower's outputs for the sample forwarded alone stay for the group it belongs to

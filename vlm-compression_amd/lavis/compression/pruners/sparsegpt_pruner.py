@@ -62,13 +62,13 @@ class _SparseGPTBlockMixin:
                     acc = fed.get(key)
                     if acc is None:
                         acc = sparsegpt.SparseGPT(subset[name])
-                        acc.add_batch(x, None)     # (`out` is None where the statistics pass cut the dead tail; add_batch never reads it, sparsegpt_pruner.py:68-79)
+                        cal.add_batch_rows(acc, name, x)     # (`out` is None where the statistics pass cut the dead tail; add_batch never reads it, sparsegpt_pruner.py:68-79)
                         fed[key] = acc
                     wrapped[name] = acc
                 elif fed.get(key) is not acc:
                     if key in fed:
                         raise RuntimeError(f"{name}: the linears sharing an input changed between calibration samples")
-                    acc.add_batch(x, None)     # (`out` is None where the statistics pass cut the dead tail; add_batch never reads it, sparsegpt_pruner.py:68-79)
+                    cal.add_batch_rows(acc, name, x)     # (`out` is None where the statistics pass cut the dead tail; add_batch never reads it, sparsegpt_pruner.py:68-79)
                     fed[key] = acc
                 acc._keep_alive = x                                   # the signature holds only while `x` lives
             return hook
@@ -261,7 +261,8 @@ class T5LayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
 
         try:
             cal.walk_blocks(model, inps, outs, caches, module_to_process, n_samples,
-                            lambda: model.maybe_autocast(dtype=torch.bfloat16), prune_block, tuple_output=True)
+                            lambda: model.maybe_autocast(dtype=torch.bfloat16), prune_block, tuple_output=True,
+                            pad_ragged=config.flag("VLMC_SGPT_PAD"))        # (opt-in; the Hessian hooks take the padded group's row map)
         finally:
             _flush_score_backlog(self)
         cfg.use_cache = use_cache

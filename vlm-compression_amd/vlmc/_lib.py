@@ -68,6 +68,7 @@ SIGNATURES = {
     "vlmc_sparse_lora_bwd_weight_workspace": (_sz, [_i64, _i64, _i64]),
     "vlmc_sparse_lora_bwd_weight": (_i, [_p, _i64, _p, _i64, _i64, _i, _i64, _i64, _p, _p, _i, _c.c_float, _i, _i, _p, _p, _p, _sz, _p]),
     "vlmc_act_moments": (_i, [_p, _i, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "vlmc_act_moments_lens": (_i, [_p, _i, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
     "vlmc_dsnot_stats_update": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _i64, _p, _p]),
     "vlmc_dsnot_refine": (_i, [_p, _i, _i64, _i64, _i64, _p, _p, _p, _p, _i, _i, _i, _i, _c.c_float, _c.c_float, _i, _p, _p, _p]),
     "vlmc_dsnot_apply": (_i, [_p, _i, _i64, _i64, _i64, _p, _p, _p, _i, _i, _i, _p]),
@@ -96,6 +97,7 @@ SIGNATURES = {
     "vlmc_sdpa_fwd": (_i, [_p, _p, _p, _p, _i] + [_i64] * 17 + [_c.c_float, _i, _p]),
     "vlmc_hessian_workspace": (_sz, [_i, _i64, _i64]),
     "vlmc_hessian_accum": (_i, [_p, _i, _i64, _i64, _i64, _p, _i64, _c.c_float, _c.c_float, _p, _sz, _p]),
+    "vlmc_hessian_accum_rows": (_i, [_p, _i, _i64, _i64, _i64, _p, _i64, _p, _i64, _c.c_float, _c.c_float, _p, _sz, _p]),
     "vlmc_symmetrize_lower": (_i, [_p, _i64, _i64, _p]),
     "vlmc_chol_block": (_i, [_p, _i64, _i, _p, _i64, _p, _i64, _p, _i, _p]),
     "vlmc_chol_inverse_workspace": (_sz, [_i64]),

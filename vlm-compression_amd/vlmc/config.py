@@ -91,6 +91,8 @@ CROSSCHECK = {
     "VLMC_TORCH_FUNCTION_MODE": ("0", "1: the replay's routing through a scoped TorchFunctionMode instead of attribute patches"),
     "VLMC_ATTN_CLAMP": ("1", "0: an attention chain with the LLaMA clamp (torch.max against finfo.min) is computed op by op from the clamp on"),
     "VLMC_ROPE": ("1", "0: apply_rotary_pos_emb of a LLaMA attention runs as the model file's ~16 launches"),
+    "VLMC_DSNOT_PAD": ("1", "0: the DSnoT pruners forward ragged samples in groups of equal shape (their statistic without per-sample token counts)"),
+    "VLMC_SGPT_PAD": ("0", "1: the SparseGPT pruners forward ragged samples as one padded group per block pass, their Hessians over the group's row map (off: its gain over the groups of equal shape was within the measurement's spread, profiles/ragged_dsnot_sparsegpt.md)"),
     "VLMC_GROUP_VIEWS": ("1", "0: a merged forward's group is handed copies of a finished tower's block outputs, not views"),
 }
 

@@ -51,6 +51,8 @@ ROUTES = {
     "gelu_torch": ({"VLMC_GELU": "0"}, "torch's GELU kernel (another instruction sequence in a tensor's last partial block)"),
     "attn_unfused": ({"VLMC_ATTN_FUSED": "0"}, "an attention written op by op runs op by op (vlmc_attn_matmul, torch elementwise, vlmc_softmax_rows) instead of vlmc_attn_fwd"),
     "replay_equal_shapes": ({"VLMC_PAD_RAGGED": "0", "VLMC_TOWER_PAD": "0"}, "ragged samples forwarded in groups of equal shape, never padded"),
+    "dsnot_equal_shapes": ({"VLMC_DSNOT_PAD": "0"}, "DSnoT's walk forwards ragged samples in groups of equal shape (vlmc_act_moments, no per-sample token counts)"),
+    "sparsegpt_padded_groups": ({"VLMC_SGPT_PAD": "1"}, "SparseGPT's walk forwards ragged samples as one padded group per block pass (vlmc_hessian_accum_rows over the group's row map)"),
     "towers_per_length": ({"VLMC_TOWER_PAD": "0"}, "a finished tower runs one stacked pass per token count"),
     "wiring_per_signature": ({"VLMC_TOWER_SHARE_WIRING": "0"}, "a finished tower is traced once per exact argument signature"),
     "capture_per_sample_behind_pruned": ({"VLMC_CAPTURE_MERGED_PRUNED": "0"}, "ragged batches with a pruned tower on the way (the decoder's phase) are captured one forward per sample"),

@@ -44,17 +44,30 @@ def stats_update(in_features, device, normsq, sums, vars_, tokens, batch):
     return scaler, sum_row, var_row, sqrt_row, (normsq, sums, vars_, tok)
 
 
-def act_moments_calls(x: torch.Tensor, calls: int) -> torch.Tensor:
+def act_moments_calls(x: torch.Tensor, calls: int, call_tokens: torch.Tensor | None = None) -> torch.Tensor:
     """[3, calls, in] fp32 for `calls` hook calls stacked along dim 0 of x [calls * b, tokens, in] (a grouped replay
     forward, calibration.stacked_samples): the same per-call moments as `act_moments`, ONE launch for all of them
-    (a launch per sample and distinct linear input was 54 000 launches -- 0.7 s of host time -- per FlanT5-XL prune)."""
+    (a launch per sample and distinct linear input was 54 000 launches -- 0.7 s of host time -- per FlanT5-XL prune).
+    `call_tokens` (int32 device tensor [calls]; x [calls, padded tokens, in]): a PADDED group of ragged samples -- call c owns its
+    first call_tokens[c] token rows, the rest is padding that is not read (`vlmc_act_moments_lens`); its moments are the bits of
+    `act_moments` on that sample alone."""
+    if call_tokens is not None and x.shape[0] != calls:
+        raise ValueError(f"act_moments_calls: per-call token counts need one sample per call (got {x.shape[0]} rows for {calls} calls)")
     x = x.reshape(calls, -1, x.shape[-1])
     if x.stride(-1) != 1:
         x = x.contiguous()
     _need_gpu(x)
     out = torch.empty((3, calls, x.shape[-1]), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().vlmc_act_moments(x.data_ptr(), _dtype_code(x), calls, x.shape[1], x.shape[2], x.stride(1), x.stride(0),
-                                            out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _stream()))
+    if call_tokens is None:
+        _lib.check(_lib.load().vlmc_act_moments(x.data_ptr(), _dtype_code(x), calls, x.shape[1], x.shape[2], x.stride(1), x.stride(0),
+                                                out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _stream()))
+        return out
+    _need_gpu(call_tokens)
+    if call_tokens.dtype != torch.int32 or call_tokens.numel() != calls or not call_tokens.is_contiguous():
+        raise ValueError("act_moments_calls: call_tokens must be a contiguous int32 tensor with one entry per call")
+    _lib.check(_lib.load().vlmc_act_moments_lens(x.data_ptr(), _dtype_code(x), calls, x.shape[1], x.shape[2], x.stride(1), x.stride(0),
+                                                 call_tokens.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                                 _stream()))
     return out
 
 
@@ -74,12 +87,23 @@ class DsnotInputStat:
         x = x.reshape(1, -1, x.shape[-1])
         self.blocks.append((act_moments(x).unsqueeze(1), [x.shape[1]], [b], None if sample is None else [sample]))
 
-    def add_calls(self, x: torch.Tensor, calls: int, samples):
-        """x [calls * b, tokens, in]: `calls` hook calls of the reference in one tensor, for calibration samples `samples`."""
-        if calls == 1:
-            return self.add_call(x, samples[0])
-        b = x.shape[0] // calls
-        self.blocks.append((act_moments_calls(x, calls), [b * x.shape[1]] * calls, [b] * calls, list(samples)))
+    def add_calls(self, x: torch.Tensor, calls: int, samples, call_tokens=None, host_tokens=None):
+        """x [calls * b, tokens, in]: `calls` hook calls of the reference in one tensor, for calibration samples `samples`.
+        `call_tokens` (int32 device tensor [calls]) with `host_tokens` (the same counts on the host: the group's plan has them, nothing
+        is read back): x [calls, padded tokens, in] is a PADDED group of ragged samples; every call's record holds its sample's OWN
+        token count (the variance merge of `vlmc_dsnot_stats_update` weighs by it, dsnot_pruner.py:92)."""
+        if call_tokens is None:
+            if calls == 1:
+                return self.add_call(x, samples[0])
+            b = x.shape[0] // calls
+            self.blocks.append((act_moments_calls(x, calls), [b * x.shape[1]] * calls, [b] * calls, list(samples)))
+            return
+        tokens = [int(t) for t in host_tokens] if host_tokens is not None else []
+        if x.dim() != 3 or x.shape[0] != calls or len(tokens) != calls:
+            raise ValueError("DsnotInputStat.add_calls: per-sample lengths need x [calls, padded tokens, in] and one host count per call")
+        if min(tokens) < 1 or max(tokens) > x.shape[1]:
+            raise ValueError(f"DsnotInputStat.add_calls: token counts must lie in 1 .. {x.shape[1]} (got {min(tokens)} .. {max(tokens)})")
+        self.blocks.append((act_moments_calls(x, calls, call_tokens=call_tokens), tokens, [1] * calls, list(samples)))
 
     def extend(self, other: "DsnotInputStat"):
         """Append the call records of `other` (used when hook-level records are merged per linear input)."""

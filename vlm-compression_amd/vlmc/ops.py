@@ -691,9 +691,12 @@ def unpack_24(values: torch.Tensor, meta: torch.Tensor, want_mask: bool = True):
     return w, mask
 
 
-def hessian_accum(H: torch.Tensor, x: torch.Tensor, alpha: float, beta: float) -> torch.Tensor:
+def hessian_accum(H: torch.Tensor, x: torch.Tensor, alpha: float, beta: float, rows=None) -> torch.Tensor:
     """H = alpha * H + beta * x^T x on the tiles on and below the diagonal (SparseGPT.add_batch, sparsegpt_pruner.py:76-79,
-    with alpha = n/(n+b) and beta = 2/(n+b)); x [rows, in] fp16 / bf16 / fp32.  `symmetrize_lower(H)` completes H."""
+    with alpha = n/(n+b) and beta = 2/(n+b)); x [rows, in] fp16 / bf16 / fp32.  `symmetrize_lower(H)` completes H.
+    `rows` = (int32 device row map, number of real rows) of a padded group of ragged samples (replay_padding.row_map): only rows
+    row_map[0 .. n_rows) of x enter the product, gathered inside the kernel's pre-pass (`vlmc_hessian_accum_rows`); the others are
+    not read."""
     _need_gpu(H, x)
     assert H.dtype == torch.float32 and H.dim() == 2 and H.shape[0] == H.shape[1] == x.shape[-1] and H.stride(1) == 1
     x2 = x.reshape(-1, x.shape[-1])
@@ -701,10 +704,20 @@ def hessian_accum(H: torch.Tensor, x: torch.Tensor, alpha: float, beta: float) -
         x2 = x2.contiguous()
     lib = _lib.load()
     code = _dtype_code(x2)
-    need = lib.vlmc_hessian_workspace(code, x2.shape[0], x2.shape[1])
+    if rows is None:
+        need = lib.vlmc_hessian_workspace(code, x2.shape[0], x2.shape[1])
+        ws = _hessian_ws.get(need, x.device)
+        _lib.check(lib.vlmc_hessian_accum(x2.data_ptr(), code, x2.shape[0], x2.shape[1], x2.stride(0), H.data_ptr(), H.stride(0),
+                                          float(alpha), float(beta), ws.data_ptr(), ws.numel(), _stream()))
+        return H
+    row_map, n_rows = rows
+    _need_gpu(row_map)
+    if row_map.dtype != torch.int32 or not row_map.is_contiguous() or not 0 < n_rows <= row_map.numel() or row_map.numel() > x2.shape[0]:
+        raise ValueError(f"hessian_accum: a row map of {row_map.numel()} int32 entries with {n_rows} real rows does not fit x of {x2.shape[0]} rows")
+    need = lib.vlmc_hessian_workspace(code, n_rows, x2.shape[1])
     ws = _hessian_ws.get(need, x.device)
-    _lib.check(lib.vlmc_hessian_accum(x2.data_ptr(), code, x2.shape[0], x2.shape[1], x2.stride(0), H.data_ptr(), H.stride(0),
-                                      float(alpha), float(beta), ws.data_ptr(), ws.numel(), _stream()))
+    _lib.check(lib.vlmc_hessian_accum_rows(x2.data_ptr(), code, x2.shape[0], x2.shape[1], x2.stride(0), row_map.data_ptr(), int(n_rows),
+                                           H.data_ptr(), H.stride(0), float(alpha), float(beta), ws.data_ptr(), ws.numel(), _stream()))
     return H
 
 

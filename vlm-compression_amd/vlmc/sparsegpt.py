@@ -70,14 +70,18 @@ class SparseGPT:
         self._lower_only = False
         self._H = value
 
-    def _accumulate(self, X, alpha, beta):
+    def _accumulate(self, X, alpha, beta, rows=None):
         """H <- alpha H + beta X^T X (:76-79).  `vlmc_hessian_accum` (hand-written MFMA SYRK: 16-bit products are exact in
-        fp32; lower-triangle tiles only) for 16-bit activations; fp32 activations and `VLMC_SGPT_SYRK=0`: the library GEMM."""
+        fp32; lower-triangle tiles only) for 16-bit activations; fp32 activations and `VLMC_SGPT_SYRK=0`: the library GEMM.
+        `rows` = (row map, real rows) of a padded group: `vlmc_hessian_accum_rows` gathers them in its pre-pass."""
         if _SYRK and (X.dtype != torch.float32 or _SYRK_F32):
-            ops.hessian_accum(self._H, X, alpha, beta)
+            if rows is None:
+                ops.hessian_accum(self._H, X, alpha, beta)
+            else:
+                ops.hessian_accum(self._H, X, alpha, beta, rows=rows)
             self._lower_only = True
         else:
-            Xf = X.float()
+            Xf = (X if rows is None else X.index_select(0, rows[0][:rows[1]])).float()
             self._H.addmm_(Xf.t(), Xf, beta=alpha, alpha=beta)
 
     @torch.no_grad()
@@ -91,24 +95,30 @@ class SparseGPT:
         self._staged, self._staged_elems = [], 0
 
     @torch.no_grad()
-    def add_batch(self, inp, out=None):
+    def add_batch(self, inp, out=None, rows=None):
+        """`rows` = (int32 device row map, number of real rows) when `inp` [samples, padded tokens, in] is a PADDED group of ragged
+        calibration samples (replay_padding.row_map): the update is over the samples' own token rows only, the padding rows are
+        not read.  The samples of the call are counted as ever (b = inp.shape[0])."""
         if inp.dim() == 2:
             inp = inp.unsqueeze(0)
         b = inp.shape[0]
         x = inp.reshape(-1, inp.shape[-1])
+        if rows is not None and not 0 < rows[1] <= rows[0].numel() <= x.shape[0]:
+            raise ValueError(f"add_batch: a row map of {rows[0].numel()} entries, {rows[1]} real, does not fit {x.shape[0]} rows")
         # rows of X seen so far: X^T X of fewer rows than columns is singular, which decides the factorization route
-        self.factor_cache["rows_seen"] = self.factor_cache.get("rows_seen", 0) + x.shape[0]
+        self.factor_cache["rows_seen"] = self.factor_cache.get("rows_seen", 0) + (x.shape[0] if rows is None else rows[1])
         if _DEFER:
             self.nsamples += b
-            if not self._staged and x.numel() * 4 > _DEFER_BYTES:
+            if not self._staged and (rows is not None or x.numel() * 4 > _DEFER_BYTES):
                 # a grouped forward hands over all its samples in ONE call: folded in at once with the very formula `_fold`
                 # would apply to it alone -- no copy of the activations (92-404 MB per ViT-g input) is kept
                 n = self.nsamples
-                self._accumulate(x, self._folded / n, 2.0 / n)                  # :76-79 with b = this call's samples
+                self._accumulate(x, self._folded / n, 2.0 / n, rows)            # :76-79 with b = this call's samples
                 self._folded = n
                 return
-            self._staged.append(x.clone())               # the caller may reuse the activation's memory (graph replay)
-            self._staged_elems += x.numel()
+            # the caller may reuse the activation's memory (graph replay)
+            self._staged.append(x.clone() if rows is None else x.index_select(0, rows[0][:rows[1]]))
+            self._staged_elems += self._staged[-1].numel()
             if self._staged_elems * 4 > _DEFER_BYTES:
                 self._fold()
             return
@@ -116,8 +126,10 @@ class SparseGPT:
         self.nsamples += b
         self._folded = self.nsamples
         if _SYRK and (x.dtype != torch.float32 or _SYRK_F32):
-            self._accumulate(x, beta, 2.0 / self.nsamples)            # the scale 2/n rides in the epilogue
+            self._accumulate(x, beta, 2.0 / self.nsamples, rows)      # the scale 2/n rides in the epilogue
         else:
+            if rows is not None:
+                x = x.index_select(0, rows[0][:rows[1]])
             xs = math.sqrt(2 / self.nsamples) * x.float()             # :78 (scaled in fp32 before the product)
             self._H.addmm_(xs.t(), xs, beta=beta, alpha=1.0)          # H *= beta; H += xs^T xs  (:76-79)
 
