@@ -128,8 +128,11 @@ int vlmc_wanda_scaler_update_batch(const vlmc_update_job *jobs /* host array */,
  * `k` is computed by the caller exactly like the reference (int(in*ratio) or
  * int(out*in*ratio)).  Only SEL_MATRIX needs a workspace (else size 0, NULL is fine).  A SEL_MATRIX
  * workspace must be ZERO-FILLED when it is first handed to the library (hipMemset once after allocating
- * it); every call returns it zero-filled again, so it can be reused as is.  (The workgroups of one launch
- * agree on the threshold through counters in it; clearing them inside the call would cost a launch.)
+ * it); every call leaves the counters and histograms it reads before it writes them (the leading 8320 bytes among them) ZERO again, so the workspace
+ * can be reused as is by any later SEL_MATRIX call, whatever its shape and layout.  The rest of it (key slots,
+ * candidate lists) is scratch: written before it is read, content unspecified after a call -- do not expect the
+ * whole buffer to read as zeros.  (The workgroups of one launch agree on the threshold through counters in it;
+ * clearing them inside the call would cost a launch.)
  *
  * vlmc_wanda_select_batch does the same for several linears -- the `for name in subset` loop of
  * wanda_pruner.py:316-341 -- with as few launches as the shapes allow (SEL_ROW: one per distinct
@@ -476,7 +479,9 @@ int vlmc_chol_block(const float *A, int64_t lda, int nb, float *L, int64_t ldl, 
  * vlmc_chol_inverse_workspace(n) bytes of device memory, cleared by the call.
  * `max_workgroups` bounds the grid (0: one workgroup per tile task of a column pair, at most n/128 squared) so that
  * several factorizations can share the chip (each workgroup takes a whole CU's LDS).  The summation order of every tile
- * is fixed: the result does not depend on the number of workgroups.                                              */
+ * is fixed: the result does not depend on the number of workgroups.  Layout: lda, ldm, ldx multiples of 4 and A, M, X 16-byte
+ * aligned (whole tiles move in 16-byte pieces); anything else is VLMC_EINVAL ("row strides must be >= n and multiples of 4",
+ * "matrices must be 16-byte aligned").                                                                              */
 size_t vlmc_chol_inverse_workspace(int64_t n);
 int vlmc_chol_inverse(const float *A, int64_t n, int64_t lda, float *M, int64_t ldm, float *X, int64_t ldx, int *info,
                       void *workspace, size_t workspace_bytes, int max_workgroups, void *stream);
@@ -555,7 +560,11 @@ int vlmc_dsnot_stats_update(float *scaler_row, float *sum_row, float *var_row, i
  *   or :407-552 (n:m) for every row, starting from keep_mask0 (1 = keep: the initial mask, i.e.
  *   vlmc_wanda_select with k = round(in*ratio) or n:m, apply_zero = 0).  Writes, per row and cycle,
  *   events[row, t] = p | r << 14 | update << 28 for max_cycle cycles, and stop_cycle[row] = first
- *   cycle (1-based) after which the row no longer updates (INT_MAX if it never stops).
+ *   cycle (1-based) after which the row no longer updates (INT_MAX if it never stops).  Layout (vlmc_dsnot_refine_kind alike):
+ *   in_features and ldw multiples of 8, W 16-byte aligned, keep_mask0 8-byte aligned with row stride in_features -- the rows are
+ *   read in 16-byte chunks only; any other layout is VLMC_EINVAL ("needs in_features % 8 == 0 and 16-byte aligned rows").  The
+ *   replay refines whole `nn.Linear.weight` tensors, which have this layout; vlmc_dsnot_apply takes any pitch and alignment of W
+ *   and any alignment of keep_mask (row stride in_features).
  * vlmc_dsnot_apply: replays the first min(*ncycles, max_cycle) events of every row into the mask
  *   (the reference runs all rows for as long as ANY row updates: ncycles = max over rows of
  *   stop_cycle) and zeroes the pruned weights when apply_zero.  in_features <= 16384.          */
