@@ -172,7 +172,7 @@ def _worker_sparsegpt_pruner(rank, world, port, out_dir):
 @pytest.mark.timeout(600)
 def test_sample_sharded_sparsegpt_pruner_world2_tracks_reference_golden(tmp_path):
     """SparseGPT under sample sharding: every rank accumulates the Hessian of its samples, ONE all-reduce per
-    linear forms the sample-weighted mean (lavis/compression/pruners/sparsegpt_pruner.py here: _allreduce_hessians).
+    linear forms the sample-weighted mean (lavis/compression/pruners/tower_walk.py here: SharedHessians.allreduce).
     The sum order differs from the sequential running mean, so parity is the SparseGPT tolerance: both ranks
     identical to each other, zero pattern and weights close to the reference's single-process run."""
     import golden_io

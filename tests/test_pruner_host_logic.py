@@ -490,18 +490,20 @@ def test_deferred_importance_scores_survive_a_failing_tower(monkeypatch):
     spec = "2-0.5-1.0-1.0"
     pruner = load_pruner("blipt5_wanda_pruner", model, batches, cfg=dict(t5_prune_spec=spec, vit_prune_spec=spec, t5_pruning_method="wanda",
                                                                          vit_pruning_method="wanda", num_samples=4, max_sparsity_per_layer=1.01))
-    real = wp.T5LayerWandaPruner._prune
+    real = wp.BLIPT5LayerWandaPruner._prune
 
-    def boom(self, *a, **k):
+    def boom(self, kind, *a, **k):
+        if kind.vit:
+            return real(self, kind, *a, **k)
         raise RuntimeError("tower failed")
-    monkeypatch.setattr(wp.T5LayerWandaPruner, "_prune", boom)
+    monkeypatch.setattr(wp.BLIPT5LayerWandaPruner, "_prune", boom)
     with pytest.raises(RuntimeError, match="tower failed"):
         pruner.prune()
     assert pruner._defer_score_readback is False and not pruner.__dict__.get("_score_backlog")
     scored = [n for n, m in model.named_modules() if isinstance(m, torch.nn.Linear) and "visual_encoder.blocks" in n
               and hasattr(m.weight, "importance_score")]
     assert len(scored) == 2 * 4                                # the ViT tower was done: its scores are there
-    monkeypatch.setattr(wp.T5LayerWandaPruner, "_prune", real)
+    monkeypatch.setattr(wp.BLIPT5LayerWandaPruner, "_prune", real)
 
 
 @pytest.mark.parametrize("method", ["wanda", "dsnot"])

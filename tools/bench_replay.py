@@ -33,14 +33,14 @@ def run(kind, group, n=128, graph=False):
         block = toy_models.ToyViTBlock(1408, 6144, heads=16).to(torch.float16)
         xs = [(torch.randn(1, 257, 1408) * 0.5).to(torch.float16).to(dev) for _ in range(n)]
         caches = [{"rel_pos_bias": None} for _ in range(n)]
-        mode, tuple_out = "matrix", False
+        tuple_out = False
     else:
         block = toy_models.ToyT5Block(2048, 5120, heads=32, is_decoder=False).to(torch.bfloat16)
         xs = [(torch.randn(1, 64, 2048) * 0.5).to(torch.bfloat16).to(dev) for _ in range(n)]
         caches = [dict(attention_mask=None, position_bias=None, encoder_hidden_states=None, encoder_attention_mask=None,
                        encoder_decoder_position_bias=None, layer_head_mask=None, cross_attn_layer_head_mask=None)
                   for _ in range(n)]
-        mode, tuple_out = "row", True
+        tuple_out = True
     model = Tower(block.to(dev).eval(), kind == "vit")
     os.environ["VLMC_BATCH_REPLAY"] = str(group)
     os.environ["VLMC_GRAPH_REPLAY"] = "1" if graph else "0"
@@ -52,8 +52,8 @@ def run(kind, group, n=128, graph=False):
             return 0.5
 
     def prune_block(i, layer, subset, run_pass, state):
-        helper._wanda_block(i, subset, run_pass, n, 1, unstructured_mode=mode, module_to_process="blocks",
-                            model_prefix="bench", sparsity_ratio=Ratio(), lora_model=True)   # weights stay dense: repeatable
+        helper._block_step(i, subset, run_pass, n, 1, kind=helper.tower_kind, module_to_process="blocks",
+                           model_prefix="bench", sparsity_ratio=Ratio(), lora_model=True)   # weights stay dense: repeatable
 
     outs = [None] * n
     for rep in range(3):

@@ -24,7 +24,7 @@ print(f"profiled prune {dt * 1e3:.1f} ms")
 st = pstats.Stats(pr)
 rows = []
 for (fn, line, name), (cc, nc, tt, ct, callers) in st.stats.items():
-    if any(k in fn for k in ("wanda_pruner.py", "layer_single_base_pruner.py", "base_pruner.py", "pruners/utils.py", "synthetic.py")) or \
+    if any(k in fn for k in ("wanda_pruner.py", "tower_walk.py", "layer_single_base_pruner.py", "base_pruner.py", "pruners/utils.py", "synthetic.py")) or \
             name in ("capture_block_inputs", "walk_blocks", "_importance_readback", "quiet_gc", "collect"):
         rows.append((ct, tt, nc, os.path.basename(fn), line, name))
 for ct, tt, nc, fn, line, name in sorted(rows, reverse=True)[:45]:

@@ -19,17 +19,17 @@ dev = torch.device("cuda:0")
 model = synthetic.InstructBlipT5().to(dev).eval()
 batches = synthetic.calibration_batches(128, dev, vocab=model.t5_model.shared.num_embeddings)
 marks = []
-real = WP.BLIPT5LayerWandaPruner._tower
+real = WP.BLIPT5LayerWandaPruner._prune
 mark_buf = torch.zeros(7, device=dev)
 
 
-def timed(self, cls, **kw):
+def timed(self, kind, *args, **kw):
     from vlmc import phases
     torch.cuda.synchronize()
     mark_buf.cumsum_(0)                       # a kernel that appears nowhere else: the tower's first
     before = dict(phases.times)
     t0 = time.perf_counter()
-    out = real(self, cls, **kw)
+    out = real(self, kind, *args, **kw)
     torch.cuda.synchronize()
     marks.append((kw["module_to_process"], round((time.perf_counter() - t0) * 1e3, 2)))
     mark_buf.cumsum_(0)                       # ... and its last
@@ -38,7 +38,7 @@ def timed(self, cls, **kw):
     return out
 
 
-WP.BLIPT5LayerWandaPruner._tower = timed
+WP.BLIPT5LayerWandaPruner._prune = timed
 for it in range(int(os.environ.get("RANK_TIMELINE_ITERS", "7"))):
     marks.clear()
     os.environ["VLMC_PHASE_TIMERS"] = "1" if it == 6 else "0"

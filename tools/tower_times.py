@@ -14,13 +14,13 @@ dev = torch.device("cuda:0")
 model = synthetic.InstructBlipT5().to(dev).eval()
 batches = synthetic.calibration_batches(128, dev, vocab=model.t5_model.shared.num_embeddings)
 times = {}
-real = WP.BLIPT5LayerWandaPruner._tower
+real = WP.BLIPT5LayerWandaPruner._prune
 
 
 PROFILE = {"on": False, "pr": None}
 
 
-def timed(self, cls, **kw):
+def timed(self, kind, *args, **kw):
     from vlmc import phases
     torch.cuda.synchronize()
     before = dict(phases.times)
@@ -30,7 +30,7 @@ def timed(self, cls, **kw):
         PROFILE["pr"] = cProfile.Profile()
         PROFILE["pr"].enable()
     t0 = time.perf_counter()
-    out = real(self, cls, **kw)
+    out = real(self, kind, *args, **kw)
     torch.cuda.synchronize()
     if prof:
         PROFILE["pr"].disable()
@@ -41,7 +41,7 @@ def timed(self, cls, **kw):
     return out
 
 
-WP.BLIPT5LayerWandaPruner._tower = timed
+WP.BLIPT5LayerWandaPruner._prune = timed
 for w in [int(a) for a in sys.argv[1:]] or [1, 8]:
     if w > 1:
         os.environ["VLMC_SIMULATE_WORLD"] = str(w)

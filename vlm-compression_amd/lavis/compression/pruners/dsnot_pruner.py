@@ -31,6 +31,9 @@ Differences that are visible to a caller:
   reconstructed (no OBS update), only masked;
 * `max_cycle_time >= in_features` raises instead of indexing out of range.
 
+This module holds the DSnoT statistics, options, per-block step and the BLIP pruner's gating; the tower step, the tower
+sequence, the constructor keywords and the shared SparseGPT Hessians (`initial_method="sparsegpt"`) are in `tower_walk.py`.
+
 There is no CPU fallback: without the HIP library or a GPU model the pruner raises.
 """
 from __future__ import annotations
@@ -40,8 +43,10 @@ import torch
 
 from lavis.common.registry import registry
 from lavis.compression.pruners import calibration as cal
-from lavis.compression.pruners.layer_single_base_pruner import LayerSparsity, LayerWiseBasePruner
+from lavis.compression.pruners.tower_walk import (SharedHessians, TowerKind, TowerPruner, autocast_bf16,
+                                                  input_signature)
 from lavis.compression.pruners.utils import print_time
+from lavis.compression.pruners.wanda_pruner import uniform_or_layer_sparsity
 from vlmc import config
 
 _VERBOSE = config.flag("VLMC_VERBOSE")
@@ -60,8 +65,8 @@ class DsnotStatCollector:
         self._cur = -1
         # initial_method="sparsegpt": per linear the SparseGPT Hessian accumulator of its input (shared like the statistics);
         # None on the other routes (no launches, no memory)
-        self.hessians = {} if hessians else None
-        self._fed = {}                                    # input signature -> accumulator fed in this sample
+        self._shared = SharedHessians(subset) if hessians else None
+        self.hessians = self._shared.wrapped if hessians else None
         self.handles = [m.register_forward_hook(self._make_hook(n)) for n, m in subset.items()]
 
     def _make_hook(self, name):
@@ -69,7 +74,7 @@ class DsnotStatCollector:
             x = inp[0].data
             if x.dim() == 2:
                 x = x.unsqueeze(0)
-            key = (x.data_ptr(), tuple(x.shape), tuple(x.stride()), x.dtype, x._version)
+            key = input_signature(x)
             hit = self._cache.get(key)
             if hit is None:
                 stacked = cal.stacked_samples()              # batched replay: one record per stacked calibration sample
@@ -88,32 +93,14 @@ class DsnotStatCollector:
                 hit = (x, st)                                # `x` stays referenced until the next sample (see wanda collector)
                 self._cache[key] = hit
             self.calls[name].append(hit[1])
-            if self.hessians is not None:
-                self._add_hessian(name, key, x)
+            if self._shared is not None:
+                self._shared.add(name, key, x)
         return hook
-
-    def _add_hessian(self, name, key, x):
-        """The sparsegpt_pruner's sharing rule: the first sample finds which linears receive the same tensor; each distinct input
-        is folded into its accumulator once per hook call (a stacked replay's call counts its samples: the accumulator's rule)."""
-        from vlmc import sparsegpt
-        acc = self.hessians.get(name)
-        if acc is None:
-            acc = self._fed.get(key)
-            if acc is None:
-                acc = sparsegpt.SparseGPT(self.subset[name])
-                cal.add_batch_rows(acc, name, x)
-                self._fed[key] = acc
-            self.hessians[name] = acc
-        elif self._fed.get(key) is not acc:
-            if key in self._fed:
-                raise RuntimeError(f"{name}: the linears sharing an input changed between calibration samples")
-            cal.add_batch_rows(acc, name, x)
-            self._fed[key] = acc
-        acc._keep_alive = x                                   # the signature holds only while `x` lives
 
     def next_sample(self, j=None):
         self._cache.clear()
-        self._fed.clear()
+        if self._shared is not None:
+            self._shared.begin_forward()
         self._cur = self._cur + 1 if j is None else j
 
     def close(self):
@@ -121,7 +108,8 @@ class DsnotStatCollector:
             h.remove()
         self.handles = []
         self._cache.clear()
-        self._fed.clear()
+        if self._shared is not None:
+            self._shared.begin_forward()
 
     def finalize(self):
         """{name: DsnotInputStat}; linears whose hooks saw identical tensors share the object."""
@@ -145,11 +133,10 @@ class DsnotStatCollector:
     def _divisors(self, stats):
         """Sample-sharded runs exchange the Hessians (the sample-weighted mean, as the SparseGPT pruner); then every distinct
         input's divisor goes onto its statistic and the H buffers are freed."""
-        from lavis.compression.pruners.sparsegpt_pruner import _allreduce_hessians
         from vlmc.shard import require_real_exchange
-        unique = list({id(a): a for a in self.hessians.values()}.values())
+        unique = self._shared.unique()
         require_real_exchange("blipt5_dsnot_pruner (initial_method='sparsegpt')")
-        _allreduce_hessians(unique)
+        self._shared.allreduce()
         acc_of_stat = {}
         for name, acc in self.hessians.items():
             if acc_of_stat.setdefault(id(stats[name]), acc) is not acc:
@@ -163,11 +150,27 @@ class DsnotStatCollector:
         self.hessians = {}
 
 
-class _DsnotBlockMixin:
-    """Per-block DSnoT step; the reference's T5/LLM and ViT `_prune` bodies are the same code."""
+_DSNOT_KW = dict(initial_method="wanda", skip_layer=None, skip_sub_layer=None, pow_of_var_regrowing=1., max_cycle_time=1e2,
+                 update_threshold=0.1, without_same_sign=True, without_DSnoT=False)
 
-    def _dsnot_block(self, i, subset, run_pass, n_inps, batch0, *, module_to_process, model_prefix, sparsity_ratio,
-                     lora_model):
+
+class _DsnotPruner(TowerPruner):
+    """The DSnoT options, tower kinds and per-block step; the reference's T5/LLM and ViT `_prune` bodies are the same code,
+    and its ViT blocks run under bf16 autocast like the T5 ones (:1086, :1493)."""
+    llm_kind = TowerKind(vit=False, tuple_output=True, autocast=autocast_bf16,
+                         pad_ragged=lambda: config.flag("VLMC_DSNOT_PAD"))
+    vit_kind = TowerKind(vit=True, tuple_output=False, autocast=autocast_bf16, pad_ragged=None)
+
+    def __init__(self, model, data_loader, model_prefix, **kwargs):
+        super().__init__(model, data_loader, model_prefix, **kwargs)
+        for name, default in _DSNOT_KW.items():
+            setattr(self, name, kwargs.get(name, default))
+
+    def get_sparsity(self, original_sparsity, sparsity_ratio_granularity=None):
+        return uniform_or_layer_sparsity(self, original_sparsity, sparsity_ratio_granularity)
+
+    def _block_step(self, i, subset, run_pass, n_inps, batch0, *, kind, module_to_process, model_prefix, sparsity_ratio,
+                    lora_model):
         from vlmc import dsnot
         col = DsnotStatCollector(subset, hessians=self.initial_method == "sparsegpt")
         try:
@@ -198,223 +201,67 @@ class _DsnotBlockMixin:
                 continue
             setattr(mod, "mask", keep)                                           # True = keep (:753)
 
-    def _set_dsnot_options(self, initial_method, skip_layer, skip_sub_layer, pow_of_var_regrowing, max_cycle_time,
-                           update_threshold, without_same_sign, without_DSnoT):
-        self.initial_method = initial_method
-        self.pow_of_var_regrowing = pow_of_var_regrowing
-        self.without_same_sign = without_same_sign
-        self.without_DSnoT = without_DSnoT
-        self.update_threshold = update_threshold
-        self.skip_layer = skip_layer
-        self.skip_sub_layer = skip_sub_layer
-        self.max_cycle_time = max_cycle_time
-
-
-def _base_kwargs(loc):
-    keys = ["model", "data_loader", "prune_spec", "is_strct_pruning", "importance_scores_cache",
-            "keep_indices_or_masks_cache", "is_global", "num_samples", "model_prefix", "sparsity_ratio_granularity",
-            "max_sparsity_per_layer", "score_method", "num_data_first_stage", "num_noise", "sparsity_dict", "noise_eps",
-            "prune_per_model", "prune_n", "prune_m"]
-    return {k: loc[k] for k in keys}
-
 
 @registry.register_pruner("t5_dsnot_pruner")
-class T5LayerDSnoTPruner(LayerWiseBasePruner, _DsnotBlockMixin):
+class T5LayerDSnoTPruner(_DsnotPruner):
     """T5 / OPT / LLaMA tower (dsnot_pruner.py:107-858)."""
     pruner_name = "t5_dsnot_pruner"
+    tower_kind = _DsnotPruner.llm_kind
 
-    def __init__(self, model, data_loader, prune_spec=None, importance_scores_cache=None,
-                 keep_indices_or_masks_cache=None, is_strct_pruning=False, num_samples=64, is_global=False,
-                 model_prefix="t5_model", sparsity_ratio_granularity=None, max_sparsity_per_layer=0.8,
-                 score_method="obd_avg", num_data_first_stage=128, num_noise=1, sparsity_dict=None, noise_eps=1e-3,
-                 prune_per_model=False, skip_layer=None, skip_sub_layer=None, pow_of_var_regrowing=1.,
-                 max_cycle_time=1e2, update_threshold=0.1, without_same_sign=True, without_DSnoT=False, prune_n=0,
-                 prune_m=0, initial_method="wanda", **kwargs):
-        super().__init__(**_base_kwargs(locals()))
-        self._set_dsnot_options(initial_method, skip_layer, skip_sub_layer, pow_of_var_regrowing, max_cycle_time,
-                                update_threshold, without_same_sign, without_DSnoT)
+    def __init__(self, model, data_loader, model_prefix="t5_model", **kwargs):
+        super().__init__(model, data_loader, model_prefix, **kwargs)
 
     def forward_to_cache(self, model, batch, lora_model=False):
         return model(batch)
 
-    def get_sparsity(self, original_sparsity, sparsity_ratio_granularity=None):
-        from lavis.compression.pruners.wanda_pruner import uniform_or_layer_sparsity
-        return uniform_or_layer_sparsity(self, original_sparsity, sparsity_ratio_granularity)
-
-    def check_sparsity(self, model, module_to_process="encoder.block"):
-        layers = cal.get_module_recursive(model, module_to_process)
-        zeros = total = 0
-        for layer in layers:
-            for mod in cal.find_layers(layer).values():
-                zeros += (mod.weight.data == 0).sum().item()
-                total += mod.weight.numel()
-        return float(zeros) / total
-
-    def prepare_calibration_input_encoder(self, model, dataloader, model_prefix, n_samples,
-                                          module_to_process="encoder.block", lora_model=False):
-        cfg = getattr(model, model_prefix).config
-        use_cache, cfg.use_cache = cfg.use_cache, False
-        try:
-            return cal.capture_block_inputs(model, dataloader, n_samples, module_to_process, self.forward_to_cache,
-                                            lora_model, vit=False, model_prefix=self.model_prefix, done_towers=getattr(self, "_done_towers", None),
-                                        proxy_cache=self.__dict__.setdefault("_proxy_cache", {}))
-        finally:
-            cfg.use_cache = use_cache
-
-    @print_time
-    def _prune(self, model, dataloader, model_prefix, module_to_process="encoder.block", n_samples=64,
-               sparsity_ratio=0.5, lora_model=False):
-        cfg = getattr(model, model_prefix).config
-        use_cache, cfg.use_cache = cfg.use_cache, False
-        with torch.no_grad():
-            inps, outs, caches = self.prepare_calibration_input_encoder(model, dataloader, model_prefix, n_samples,
-                                                                        module_to_process, lora_model)
-        n_inps, batch0 = len(inps) * cal.calibration_shard()[1], inps[0].shape[0]
-
-        def prune_block(i, layer, subset, run_pass, state):
-            self._dsnot_block(i, subset, run_pass, n_inps, batch0, module_to_process=module_to_process,
-                              model_prefix=model_prefix, sparsity_ratio=sparsity_ratio, lora_model=lora_model)
-
-        cal.walk_blocks(model, inps, outs, caches, module_to_process, n_samples,
-                        lambda: model.maybe_autocast(dtype=torch.bfloat16), prune_block, tuple_output=True,
-                        pad_ragged=config.flag("VLMC_DSNOT_PAD"))    # (the statistic takes per-sample token counts, the Hessian a row map)
-        cfg.use_cache = use_cache
-        cal.release_tower_memory()
-        return model
-
     @cal.quiet_gc
     @print_time
     def prune(self, importance_scores=None, keep_indices_or_masks=None, lora_model=False):
-        dtype_record, requires_grad_record, device = self.model_setup_and_record_attributes(self.model)
-        if self.prune_spec is None:
-            return self.model, None
-        _, keep_ratio, _, _ = self.convert_spec_to_list(self.prune_spec)
-        sparsity_dict = self.get_sparsity(1 - keep_ratio, sparsity_ratio_granularity=self.sparsity_ratio_granularity)
-        for side in ("encoder", "decoder"):                                     # :842-857
-            self.model = self._prune(self.model, self.data_loader, model_prefix=self.model_prefix,
-                                     module_to_process=f"{self.model_prefix}.{side}.block", n_samples=self.num_samples,
-                                     sparsity_ratio=sparsity_dict, lora_model=lora_model)
-        self.model_reset(self.model, dtype_record, requires_grad_record, device)
-        return self.model, sparsity_dict
+        return self._prune_alone(("encoder.block", "decoder.block"), lora_model)             # :842-857
 
 
 @registry.register_pruner("vit_dsnot_pruner")
-class VITLayerDSnoTPruner(LayerWiseBasePruner, _DsnotBlockMixin):
-    """EVA ViT tower (dsnot_pruner.py:861-1596): the same per-row procedure; blocks return a
-    tensor, and the block forward runs under bf16 autocast like the T5 one (:1086, :1493)."""
+class VITLayerDSnoTPruner(_DsnotPruner):
+    """EVA ViT tower (dsnot_pruner.py:861-1596): the same per-row procedure; blocks return a tensor."""
     pruner_name = "vit_dsnot_pruner"
+    tower_kind = _DsnotPruner.vit_kind
 
-    def __init__(self, model, data_loader, prune_spec=None, importance_scores_cache=None,
-                 keep_indices_or_masks_cache=None, is_strct_pruning=False, num_samples=64, is_global=False,
-                 model_prefix="visual", sparsity_ratio_granularity=None, max_sparsity_per_layer=0.8,
-                 score_method="obd_avg", num_data_first_stage=128, num_noise=1, sparsity_dict=None, noise_eps=1e-3,
-                 prune_per_model=False, prune_n=0, prune_m=0, initial_method="wanda", skip_layer=None,
-                 skip_sub_layer=None, pow_of_var_regrowing=1., max_cycle_time=1e2, update_threshold=0.1,
-                 without_same_sign=True, without_DSnoT=False, **kwargs):
-        super().__init__(**_base_kwargs(locals()))
-        self._set_dsnot_options(initial_method, skip_layer, skip_sub_layer, pow_of_var_regrowing, max_cycle_time,
-                                update_threshold, without_same_sign, without_DSnoT)
+    def __init__(self, model, data_loader, model_prefix="visual", **kwargs):
+        super().__init__(model, data_loader, model_prefix, **kwargs)
 
     def forward_to_cache(self, model, batch, lora_model=False):
         return model.encode_image(batch["image"])
 
-    get_sparsity = T5LayerDSnoTPruner.get_sparsity
-    check_sparsity = T5LayerDSnoTPruner.check_sparsity
-
-    def prepare_calibration_input_encoder(self, model, dataloader, model_prefix, n_samples,
-                                          module_to_process="encoder.block", lora_model=False):
-        return cal.capture_block_inputs(model, dataloader, n_samples, module_to_process, self.forward_to_cache,
-                                        lora_model, vit=True, done_towers=getattr(self, "_done_towers", None),
-                                        proxy_cache=self.__dict__.setdefault("_proxy_cache", {}))
-
-    @print_time
-    def _prune(self, model, dataloader, model_prefix, module_to_process="encoder.block", n_samples=64,
-               sparsity_ratio=0.5, lora_model=False):
-        with torch.no_grad():
-            inps, outs, caches = self.prepare_calibration_input_encoder(model, dataloader, model_prefix, n_samples,
-                                                                        module_to_process, lora_model)
-        n_inps, batch0 = len(inps) * cal.calibration_shard()[1], inps[0].shape[0]
-
-        def prune_block(i, layer, subset, run_pass, state):
-            self._dsnot_block(i, subset, run_pass, n_inps, batch0, module_to_process=module_to_process,
-                              model_prefix=model_prefix, sparsity_ratio=sparsity_ratio, lora_model=lora_model)
-
-        cal.walk_blocks(model, inps, outs, caches, module_to_process, n_samples,
-                        lambda: model.maybe_autocast(dtype=torch.bfloat16), prune_block, tuple_output=False,
-                        memo_cache=self.__dict__.get("_proxy_cache"))
-        cal.release_tower_memory()
-        return model
-
     @cal.quiet_gc
     @print_time
     def prune(self, importance_scores=None, keep_indices_or_masks=None, lora_model=False):
-        dtype_record, requires_grad_record, device = self.model_setup_and_record_attributes(self.model)
-        if self.prune_spec is None:
-            return self.model, None
-        _, keep_ratio, _, _ = self.convert_spec_to_list(self.prune_spec)
-        sparsity_dict = self.get_sparsity(1 - keep_ratio, sparsity_ratio_granularity=self.sparsity_ratio_granularity)
-        self.model = self._prune(self.model, self.data_loader, model_prefix=self.model_prefix,
-                                 module_to_process=f"{self.model_prefix}.blocks", n_samples=self.num_samples,
-                                 sparsity_ratio=sparsity_dict, lora_model=lora_model)
-        self.model_reset(self.model, dtype_record, requires_grad_record, device)
-        return self.model, sparsity_dict
+        return self._prune_alone(("blocks",), lora_model)
 
 
 @registry.register_pruner("blipt5_dsnot_pruner")
-class BLIPT5LayerDSnoTPruner(LayerWiseBasePruner, _DsnotBlockMixin):
+class BLIPT5LayerDSnoTPruner(_DsnotPruner):
     """ViT tower, then T5 encoder, then T5 decoder (or the LLaMA/OPT stack) -- dsnot_pruner.py:1599-1878."""
     pruner_name = "blipt5_dsnot_pruner"
 
     def __init__(self, model, data_loader, t5_prune_spec=None, vit_prune_spec=None, t5_pruning_method=None,
-                 vit_pruning_method=None, t5_importance_scores_cache=None, t5_keep_indices_or_masks_cache=None,
-                 vit_importance_scores_cache=None, vit_keep_indices_or_masks_cache=None, importance_scores_cache=None,
-                 keep_indices_or_masks_cache=None, is_strct_pruning=False, num_samples=64, is_global=False,
-                 t5_model_prefix="t5_model", vit_model_prefix="visual_encoder", sparsity_ratio_granularity=None,
-                 max_sparsity_per_layer=0.8, score_method="obd_avg", num_data_first_stage=128, num_noise=1,
-                 sparsity_dict=None, noise_eps=1e-3, prune_per_model=False, initial_method="wanda", skip_layer=None,
-                 skip_sub_layer=None, pow_of_var_regrowing=1., max_cycle_time=1e2, update_threshold=0.1,
-                 without_same_sign=True, without_DSnoT=False, peft_postfix="", prune_n=0, prune_m=0, **kwargs):
-        prune_spec, model_prefix = None, f"{vit_model_prefix}+{t5_model_prefix}"
-        super().__init__(**_base_kwargs(locals()))
-        self._set_dsnot_options(initial_method, skip_layer, skip_sub_layer, pow_of_var_regrowing, max_cycle_time,
-                                update_threshold, without_same_sign, without_DSnoT)
-        self.t5_prune_spec = t5_prune_spec
-        self.vit_prune_spec = vit_prune_spec
-        self.peft_postfix = peft_postfix
-        assert t5_pruning_method is not None
-        assert vit_pruning_method is not None
-        self.t5_model_prefix = t5_model_prefix
-        self.vit_model_prefix = vit_model_prefix
+                 vit_pruning_method=None, t5_model_prefix="t5_model", vit_model_prefix="visual_encoder", peft_postfix="",
+                 **kwargs):
+        super().__init__(model, data_loader, f"{vit_model_prefix}+{t5_model_prefix}", **dict(kwargs, prune_spec=None))
+        self._set_blip_towers(t5_prune_spec, vit_prune_spec, t5_pruning_method, vit_pruning_method, t5_model_prefix,
+                              vit_model_prefix, peft_postfix)
 
     def get_sparsity(self, t5_sparsity, vit_sparsity, sparsity_ratio_granularity=None):
         """(:1683-1757): a yaml override, else LayerSparsity at the MEAN of both sparsities (per-tower budgets
-        under `prune_per_model`)."""
-        original_sparsity = 0.5 * (t5_sparsity + vit_sparsity)
-        if self.sparsity_dict is not None:
-            import yaml
-            with open(self.sparsity_dict, "r") as f:
-                return yaml.load(f, Loader=yaml.FullLoader)
-        from lavis.compression.pruners.utils import loss_vision_language
-        from lavis.compression.pruners.wanda_pruner import layer_to_group_mapping
-        # same grouping rule as the Wanda pruner's get_sparsity (:1693-1740)
-        mapping = layer_to_group_mapping(self, sparsity_ratio_granularity)
-        return LayerSparsity(self.model, self.data_loader, loss_vision_language, self.num_data_first_stage, original_sparsity,
-                             self.max_sparsity_per_layer, self.score_method, self.num_noise, self.noise_eps, mapping,
-                             prune_per_model=self.prune_per_model,
-                             per_model_group=[self.t5_model_prefix, self.vit_model_prefix],
-                             per_model_sparsity=[t5_sparsity, vit_sparsity]).return_sparsity()
+        under `prune_per_model`), with the grouping rule of the Wanda pruner's get_sparsity (:1693-1740)."""
+        return uniform_or_layer_sparsity(self, 0.5 * (t5_sparsity + vit_sparsity), sparsity_ratio_granularity,
+                                         prune_per_model=self.prune_per_model,
+                                         per_model_group=[self.t5_model_prefix, self.vit_model_prefix],
+                                         per_model_sparsity=[t5_sparsity, vit_sparsity])
 
     def forward_to_cache(self, model, batch, lora_model=False):
         if lora_model:
             return model(batch, vit_dense=True, llm_dense=True)                 # always dense here (:1759-1763)
         return model(batch)
-
-    def _tower(self, cls, **kw):
-        self.prepare_calibration_input_encoder = lambda *a, **k: cls.prepare_calibration_input_encoder(self, *a, **k)
-        out = cls._prune(self, self.model, self.data_loader, **kw)
-        # the finished tower's blocks may replay from HIP graphs while the next tower's inputs are captured
-        self._done_towers = getattr(self, "_done_towers", []) + [kw["module_to_process"]]
-        return out
 
     @cal.quiet_gc
     @print_time
@@ -427,28 +274,13 @@ class BLIPT5LayerDSnoTPruner(LayerWiseBasePruner, _DsnotBlockMixin):
             global_sparsity_dict = self.get_sparsity(1 - t5_keep_ratio, 1 - vit_keep_ratio,
                                                      sparsity_ratio_granularity=self.sparsity_ratio_granularity)
 
-        if self.vit_prune_spec is not None and float(vit_keep_ratio) < 1.:
-            s = 1 - vit_keep_ratio
-            sd = global_sparsity_dict if global_sparsity_dict is not None else \
+        def own(keep_ratio):
+            s = 1 - keep_ratio
+            return lambda: global_sparsity_dict if global_sparsity_dict is not None else \
                 self.get_sparsity(s, s, sparsity_ratio_granularity=None)
-            self.model = self._tower(VITLayerDSnoTPruner, model_prefix=self.vit_model_prefix,
-                                     module_to_process=f"{self.vit_model_prefix}.blocks", n_samples=self.num_samples,
-                                     sparsity_ratio=sd, lora_model=lora_model)
-
-        if self.t5_prune_spec is not None and float(t5_keep_ratio) < 1.:
-            s = 1 - t5_keep_ratio
-            sd = global_sparsity_dict if global_sparsity_dict is not None else \
-                self.get_sparsity(s, s, sparsity_ratio_granularity=None)
-            if "t5_model" in self.t5_model_prefix:
-                for side in ("encoder", "decoder"):
-                    self.model = self._tower(T5LayerDSnoTPruner, model_prefix=self.t5_model_prefix,
-                                             module_to_process=f"{self.t5_model_prefix}.{side}.block",
-                                             n_samples=self.num_samples, sparsity_ratio=sd, lora_model=lora_model)
-            else:
-                self.model = self._tower(T5LayerDSnoTPruner, model_prefix=self.t5_model_prefix,
-                                         module_to_process=f"{self.t5_model_prefix}{self.peft_postfix}.model.layers",
-                                         n_samples=self.num_samples, sparsity_ratio=sd, lora_model=lora_model)
-
+        self._prune_towers(lora_model,
+                           vit=own(vit_keep_ratio) if self.vit_prune_spec is not None and float(vit_keep_ratio) < 1. else None,
+                           llm=own(t5_keep_ratio) if self.t5_prune_spec is not None and float(t5_keep_ratio) < 1. else None)
         self.model_reset(self.model, dtype_record, requires_grad_record, device)
         return self.model, global_sparsity_dict
 

@@ -6,6 +6,7 @@ Same registry names, constructor kwargs and `prune(importance_scores=None,
 keep_indices_or_masks=None) -> (model, sparsity_dict | None)` contract.  Quirks kept: calibration stops by BATCH index
 (`i >= n_samples`, :391-393), both towers are pruned whenever their spec is not None (no keep-ratio < 1 test,
 :1021,:1044), no `module.mask` is attached (SparseGPT only rewrites the weights).  The arithmetic lives in `vlmc.sparsegpt`.
+The tower step, the tower sequence, the constructor keywords and the Hessian-sharing hook rule are in `tower_walk.py`.
 
 Beyond the reference:
 * `blipt5_sparsegpt_pruner` with a `t5_model_prefix` containing "llm_model" walks
@@ -28,61 +29,56 @@ import torch
 
 from lavis.common.registry import registry
 from lavis.compression.pruners import calibration as cal
-from lavis.compression.pruners.layer_single_base_pruner import LayerWiseBasePruner
+from lavis.compression.pruners.tower_walk import (SharedHessians, TowerKind, TowerPruner, autocast_bf16, autocast_default,
+                                                  input_signature)
 from lavis.compression.pruners.utils import print_time
-from vlmc import config
 from lavis.compression.pruners.wanda_pruner import uniform_or_layer_sparsity
-
-_KW = dict(prune_spec=None, importance_scores_cache=None, keep_indices_or_masks_cache=None, is_strct_pruning=False,
-           num_samples=64, is_global=False, sparsity_ratio_granularity=None, max_sparsity_per_layer=0.8,
-           score_method="obd_avg", num_data_first_stage=128, num_noise=1, sparsity_dict=None, noise_eps=1e-3,
-           prune_per_model=False, prune_n=0, prune_m=0)
+from vlmc import config
 
 
-class _SparseGPTBlockMixin:
-    def _capture(self, model, dataloader, n_samples, module_to_process, vit, model_prefix=None, lora_model=False):
-        return cal.capture_block_inputs(model, dataloader, n_samples, module_to_process, self.forward_to_cache, lora_model, vit=vit,
-                                        model_prefix=model_prefix, count_batches=True, done_towers=getattr(self, "_done_towers", None),
-                                        proxy_cache=self.__dict__.setdefault("_proxy_cache", {}))
+class _SparseGPTPruner(TowerPruner):
+    """The SparseGPT tower kinds and per-block step shared by the T5/LLM, ViT and BLIP pruners."""
+    # (padded groups of ragged text are opt-in; the Hessian hooks take the padded group's row map)
+    llm_kind = TowerKind(vit=False, tuple_output=True, autocast=autocast_bf16,
+                         pad_ragged=lambda: config.flag("VLMC_SGPT_PAD"), count_batches=True)
+    vit_kind = TowerKind(vit=True, tuple_output=False, autocast=autocast_default, pad_ragged=None, count_batches=True)
+    opt_walk = True
 
-    def _sparsegpt_block(self, i, subset, run_pass, n_inps, module_to_process, sparsity_ratio, lora_model=False):
+    def get_sparsity(self, original_sparsity, sparsity_ratio_granularity=None):
+        return uniform_or_layer_sparsity(self, original_sparsity, sparsity_ratio_granularity)
+
+    def _capture(self, kind, *args):
+        if not kind.vit:
+            print("loading calibdation data")
+        return super()._capture(kind, *args)
+
+    def _end_of_tower(self, walked):
+        _flush_score_backlog(self)                       # per tower, also when it raised
+
+    def _block_step(self, i, subset, run_pass, n_inps, batch0, *, kind, module_to_process, model_prefix, sparsity_ratio,
+                    lora_model):
         """Hooks -> one dense pass -> prune every linear (sparsegpt_pruner.py:405-459).  Linears that receive the
-        very same tensor (q/k/v, wi_0/wi_1, cross-attention k/v) have bit-identical Hessians: they share ONE
-        accumulator (one GEMM per hook input instead of one per linear) and ONE Cholesky chain.  `lora_model`: the
-        sweeps' keep masks go onto `module.mask`, the weights stay (module docstring)."""
+        very same tensor (q/k/v, wi_0/wi_1, cross-attention k/v) share ONE Hessian accumulator and ONE Cholesky chain
+        (`SharedHessians`).  `lora_model`: the sweeps' keep masks go onto `module.mask`, the weights stay (module docstring)."""
         from vlmc import sparsegpt
-        wrapped, fed = {}, {}            # linear name -> accumulator; input signature -> accumulator fed in this forward
+        shared = SharedHessians(subset)
 
         def make_hook(name):
             def hook(_m, inp, out):
                 x = inp[0].data
-                key = (x.data_ptr(), tuple(x.shape), tuple(x.stride()), x.dtype, x._version)
-                acc = wrapped.get(name)
-                if acc is None:                                       # first sample: discover who shares what
-                    acc = fed.get(key)
-                    if acc is None:
-                        acc = sparsegpt.SparseGPT(subset[name])
-                        cal.add_batch_rows(acc, name, x)     # (`out` is None where the statistics pass cut the dead tail; add_batch never reads it, sparsegpt_pruner.py:68-79)
-                        fed[key] = acc
-                    wrapped[name] = acc
-                elif fed.get(key) is not acc:
-                    if key in fed:
-                        raise RuntimeError(f"{name}: the linears sharing an input changed between calibration samples")
-                    cal.add_batch_rows(acc, name, x)     # (`out` is None where the statistics pass cut the dead tail; add_batch never reads it, sparsegpt_pruner.py:68-79)
-                    fed[key] = acc
-                acc._keep_alive = x                                   # the signature holds only while `x` lives
+                shared.add(name, input_signature(x), x)
             return hook
 
         handles = [mod.register_forward_hook(make_hook(name)) for name, mod in subset.items()]
         try:
-            run_pass(lambda _j: fed.clear(), outputs=False)
+            run_pass(lambda _j: shared.begin_forward(), outputs=False)
         finally:
             for h in handles:
                 h.remove()
-        unique = list({id(a): a for a in wrapped.values()}.values())
+        wrapped, unique = shared.wrapped, shared.unique()
         from vlmc.shard import require_real_exchange
         require_real_exchange("blipt5_sparsegpt_pruner")
-        _allreduce_hessians(unique)
+        shared.allreduce()
         owner = _shard_linears(subset, wrapped)
         rank = cal.calibration_shard()[0]
         mine = [name for name in subset if owner is None or owner[name] == rank]
@@ -213,128 +209,48 @@ def _exchange_pruned(subset, owner, rank, masks=False):
         setattr(subset[name].weight, "importance_score", float(scores[k].item()))
 
 
-def _allreduce_hessians(wrapped):
-    """Multi-GPU: every rank accumulated H over its share of the samples; the global running mean
-    is the sample-weighted average.  (Not in the reference, which runs replicas.)"""
-    import torch.distributed as dist
-    rank, world = cal.calibration_shard()
-    if world == 1:
-        return
-    for w in wrapped:
-        total = torch.tensor([float(w.nsamples)], device=w.H.device)
-        w.H.mul_(w.nsamples)
-        dist.all_reduce(w.H)
-        dist.all_reduce(total)
-        w.nsamples = int(total.item())
-        w.H.div_(w.nsamples)
-        if hasattr(w, "_folded"):
-            w._folded = w.nsamples
-
-
 @registry.register_pruner("t5_sparsegpt_pruner")
-class T5LayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
+class T5LayerSparseGPTPruner(_SparseGPTPruner):
     pruner_name = "t5_sparsegpt_pruner"
+    tower_kind = _SparseGPTPruner.llm_kind
 
     def __init__(self, model, data_loader, model_prefix="t5_model", **kwargs):
-        kw = dict(_KW); kw.update({k: v for k, v in kwargs.items() if k in _KW})
-        super().__init__(model=model, data_loader=data_loader, model_prefix=model_prefix, **kw)
+        super().__init__(model, data_loader, model_prefix, **kwargs)
 
     def forward_to_cache(self, model, batch, lora_model=False):
         return model(batch)
-
-    def get_sparsity(self, original_sparsity, sparsity_ratio_granularity=None):
-        return uniform_or_layer_sparsity(self, original_sparsity, sparsity_ratio_granularity)
-
-    @print_time
-    def _prune(self, model, dataloader, device, model_prefix, module_to_process="encoder.block", n_samples=64,
-               sparsity_ratio=0.5, lora_model=False):
-        cfg = getattr(model, model_prefix).config
-        use_cache, cfg.use_cache = cfg.use_cache, False
-        print("loading calibdation data")
-        with torch.no_grad():
-            inps, outs, caches = self._capture(model, dataloader, n_samples, module_to_process, vit=False,
-                                               model_prefix=self.model_prefix, lora_model=lora_model)
-        n_inps = len(inps) * cal.calibration_shard()[1]
-
-        def prune_block(i, layer, subset, run_pass, state):
-            self._sparsegpt_block(i, subset, run_pass, n_inps, module_to_process, sparsity_ratio, lora_model)
-
-        try:
-            cal.walk_blocks(model, inps, outs, caches, module_to_process, n_samples,
-                            lambda: model.maybe_autocast(dtype=torch.bfloat16), prune_block, tuple_output=True,
-                            pad_ragged=config.flag("VLMC_SGPT_PAD"))        # (opt-in; the Hessian hooks take the padded group's row map)
-        finally:
-            _flush_score_backlog(self)
-        cfg.use_cache = use_cache
-        cal.release_tower_memory()
-        return model
 
     @cal.quiet_gc
     @print_time
     def prune(self, importance_scores=None, keep_indices_or_masks=None, lora_model=False):
         """Encoder, then decoder (sparsegpt_pruner.py:511-543)."""
         print("In: ", self.pruner_name)
-        dtype_record, requires_grad_record, device = self.model_setup_and_record_attributes(self.model)
-        if self.prune_spec is None:
-            return self.model, None
-        _, keep_ratio, _, _ = self.convert_spec_to_list(self.prune_spec)
-        sparsity_dict = self.get_sparsity(1 - keep_ratio, sparsity_ratio_granularity=self.sparsity_ratio_granularity)
-        for side in ("encoder", "decoder"):
-            self.model = self._prune(self.model, self.data_loader, device, model_prefix=self.model_prefix,
-                                     module_to_process=f"{self.model_prefix}.{side}.block", n_samples=self.num_samples,
-                                     sparsity_ratio=sparsity_dict, lora_model=lora_model)
-        self.model_reset(self.model, dtype_record, requires_grad_record, device)
-        _release_factor_caches()
-        return self.model, sparsity_dict
+        out = self._prune_alone(("encoder.block", "decoder.block"), lora_model)
+        if self.prune_spec is not None:
+            _release_factor_caches()
+        return out
 
 
 @registry.register_pruner("vit_sparsegpt_pruner")
-class VITLayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
+class VITLayerSparseGPTPruner(_SparseGPTPruner):
     pruner_name = "vit_sparsegpt_pruner"
+    tower_kind = _SparseGPTPruner.vit_kind
 
     def __init__(self, model, data_loader, model_prefix="visual", **kwargs):
-        kw = dict(_KW); kw.update({k: v for k, v in kwargs.items() if k in _KW})
-        super().__init__(model=model, data_loader=data_loader, model_prefix=model_prefix, **kw)
+        super().__init__(model, data_loader, model_prefix, **kwargs)
 
     def forward_to_cache(self, model, batch, lora_model=False):
         return model.encode_image(batch["image"])
-
-    get_sparsity = T5LayerSparseGPTPruner.get_sparsity
-
-    @print_time
-    def _prune(self, model, dataloader, device, model_prefix, module_to_process="encoder.block", n_samples=64,
-               sparsity_ratio=0.5, lora_model=False):
-        with torch.no_grad():
-            inps, outs, caches = self._capture(model, dataloader, n_samples, module_to_process, vit=True, lora_model=lora_model)
-        n_inps = len(inps) * cal.calibration_shard()[1]
-
-        def prune_block(i, layer, subset, run_pass, state):
-            self._sparsegpt_block(i, subset, run_pass, n_inps, module_to_process, sparsity_ratio, lora_model)
-
-        try:
-            cal.walk_blocks(model, inps, outs, caches, module_to_process, n_samples, lambda: model.maybe_autocast(),
-                            prune_block, tuple_output=False, memo_cache=self.__dict__.get("_proxy_cache"))
-        finally:
-            _flush_score_backlog(self)
-        cal.release_tower_memory()
-        return model
 
     @cal.quiet_gc
     @print_time
     def prune(self, importance_scores=None, keep_indices_or_masks=None, lora_model=False):
         """The ViT blocks (sparsegpt_pruner.py:838-864)."""
         print("In: ", self.pruner_name)
-        dtype_record, requires_grad_record, device = self.model_setup_and_record_attributes(self.model)
-        if self.prune_spec is None:
-            return self.model, None
-        _, keep_ratio, _, _ = self.convert_spec_to_list(self.prune_spec)
-        sparsity_dict = self.get_sparsity(1 - keep_ratio, sparsity_ratio_granularity=self.sparsity_ratio_granularity)
-        self.model = self._prune(self.model, self.data_loader, device, model_prefix=self.model_prefix,
-                                 module_to_process=f"{self.model_prefix}.blocks", n_samples=self.num_samples,
-                                 sparsity_ratio=sparsity_dict, lora_model=lora_model)
-        self.model_reset(self.model, dtype_record, requires_grad_record, device)
-        _release_factor_caches()
-        return self.model, sparsity_dict
+        out = self._prune_alone(("blocks",), lora_model)
+        if self.prune_spec is not None:
+            _release_factor_caches()
+        return out
 
 
 def _release_factor_caches():
@@ -343,112 +259,48 @@ def _release_factor_caches():
 
 
 @registry.register_pruner("blipt5_sparsegpt_pruner")
-class BLIPT5LayerSparseGPTPruner(LayerWiseBasePruner, _SparseGPTBlockMixin):
+class BLIPT5LayerSparseGPTPruner(_SparseGPTPruner):
     pruner_name = "blipt5_sparsegpt_pruner"
 
     def __init__(self, model, data_loader, t5_prune_spec=None, vit_prune_spec=None, t5_pruning_method=None,
                  vit_pruning_method=None, t5_model_prefix="t5_model", vit_model_prefix="visual_encoder", peft_postfix="",
                  **kwargs):
-        kw = dict(_KW); kw.update({k: v for k, v in kwargs.items() if k in _KW})
-        kw["prune_spec"] = None
-        super().__init__(model=model, data_loader=data_loader, model_prefix=f"{vit_model_prefix}+{t5_model_prefix}", **kw)
-        self.t5_prune_spec = t5_prune_spec
-        self.vit_prune_spec = vit_prune_spec
-        assert t5_pruning_method is not None
-        assert vit_pruning_method is not None
-        self.t5_model_prefix = t5_model_prefix
-        self.vit_model_prefix = vit_model_prefix
-        self.peft_postfix = peft_postfix
+        super().__init__(model, data_loader, f"{vit_model_prefix}+{t5_model_prefix}", **dict(kwargs, prune_spec=None))
+        self._set_blip_towers(t5_prune_spec, vit_prune_spec, t5_pruning_method, vit_pruning_method, t5_model_prefix,
+                              vit_model_prefix, peft_postfix)
         self.vit_dense = True
         self.llm_dense = True
-
-    def get_sparsity(self, original_sparsity, sparsity_ratio_granularity=None):
-        return uniform_or_layer_sparsity(self, original_sparsity, sparsity_ratio_granularity)
 
     def forward_to_cache(self, model, batch, lora_model=False):
         if lora_model:
             return model(batch, vit_dense=self.vit_dense, llm_dense=self.llm_dense)      # (wanda_pruner.py:941-945)
         return model(batch)
 
-    def _llm_layers(self):
-        """The language model's block list: T5 has two (handled by the caller), InstructBLIP-Vicuna's LLaMA keeps its layers at
-        `{prefix}{peft_postfix}.model.layers` (wanda_pruner.py:1031-1038), anything else the reference's OPT walk (:1084)."""
-        if "llm_model" in self.t5_model_prefix:
-            return f"{self.t5_model_prefix}{self.peft_postfix}.model.layers"
-        return f"{self.t5_model_prefix}.model.decoder.layers"
-
     @cal.quiet_gc
     @print_time
     def prune(self, importance_scores=None, keep_indices_or_masks=None, lora_model=False):
+        """Without `lora_model` the reference's rule: a tower is pruned whenever its spec is not None (:1021, :1044).  With it
+        the towers and dense flags of the Wanda BLIP pruner (wanda_pruner.py:436-470) -- a tower is pruned only when its keep
+        ratio is below 1, and its calibration forward is dense exactly then -- with SparseGPT's sweeps deciding every
+        `module.mask`; no weight is written."""
         print("In: ", self.pruner_name)
-        if lora_model:
-            return self._prune_masks_only()
         dtype_record, requires_grad_record, device = self.model_setup_and_record_attributes(self.model)
+        grouped = self.sparsity_ratio_granularity not in [None, "none"] if lora_model else \
+            self.sparsity_ratio_granularity is not None
+        # (the reference reads both specs once a granularity is set: a missing one raises there)
+        keep = {part: self.convert_spec_to_list(spec)[1] if spec is not None or (grouped and not lora_model) else None
+                for part, spec in (("vit", self.vit_prune_spec), ("llm", self.t5_prune_spec))}
         global_sparsity_dict = None
-        if self.sparsity_ratio_granularity is not None:
-            _, vit_keep_ratio, _, _ = self.convert_spec_to_list(self.vit_prune_spec)
-            _, t5_keep_ratio, _, _ = self.convert_spec_to_list(self.t5_prune_spec)
-            assert vit_keep_ratio == t5_keep_ratio
-            global_sparsity_dict = self.get_sparsity(1 - vit_keep_ratio,
-                                                     sparsity_ratio_granularity=self.sparsity_ratio_granularity)
-        if self.vit_prune_spec is not None:
-            _, keep_ratio, _, _ = self.convert_spec_to_list(self.vit_prune_spec)
-            sd = global_sparsity_dict if global_sparsity_dict is not None else self.get_sparsity(1 - keep_ratio, None)
-            self.model = VITLayerSparseGPTPruner._prune(self, self.model, self.data_loader, device,
-                                                        model_prefix=self.vit_model_prefix,
-                                                        module_to_process=f"{self.vit_model_prefix}.blocks",
-                                                        n_samples=self.num_samples, sparsity_ratio=sd)
-            self._done_towers = getattr(self, "_done_towers", []) + [f"{self.vit_model_prefix}.blocks"]
-        if self.t5_prune_spec is not None:
-            _, keep_ratio, _, _ = self.convert_spec_to_list(self.t5_prune_spec)
-            sd = global_sparsity_dict if global_sparsity_dict is not None else self.get_sparsity(1 - keep_ratio, None)
-            if "t5_model" in self.t5_model_prefix:
-                for side in ("encoder", "decoder"):
-                    self.model = T5LayerSparseGPTPruner._prune(self, self.model, self.data_loader, device,
-                                                               model_prefix=self.t5_model_prefix,
-                                                               module_to_process=f"{self.t5_model_prefix}.{side}.block",
-                                                               n_samples=self.num_samples, sparsity_ratio=sd)
-                    self._done_towers = getattr(self, "_done_towers", []) + [f"{self.t5_model_prefix}.{side}.block"]
-            else:
-                self.model = T5LayerSparseGPTPruner._prune(self, self.model, self.data_loader, device,
-                                                           model_prefix=self.t5_model_prefix,
-                                                           module_to_process=self._llm_layers(),
-                                                           n_samples=self.num_samples, sparsity_ratio=sd)
-        self.model_reset(self.model, dtype_record, requires_grad_record, device)
-        _release_factor_caches()
-        return self.model, global_sparsity_dict
-
-    def _prune_masks_only(self):
-        """`prune(lora_model=True)`: the towers and dense flags of the Wanda BLIP pruner (wanda_pruner.py:436-470) -- a tower is
-        pruned only when its keep ratio is below 1, and its calibration forward is dense exactly then -- with SparseGPT's
-        sweeps deciding every `module.mask`; no weight is written."""
-        dtype_record, requires_grad_record, device = self.model_setup_and_record_attributes(self.model)
-        keep = {}
-        for tower, spec in (("vit", self.vit_prune_spec), ("llm", self.t5_prune_spec)):
-            keep[tower] = None if spec is None else self.convert_spec_to_list(spec)[1]
-        global_sparsity_dict = None
-        if self.sparsity_ratio_granularity not in [None, "none"]:
+        if grouped:
             assert keep["vit"] == keep["llm"]
             global_sparsity_dict = self.get_sparsity(1 - keep["llm"], sparsity_ratio_granularity=self.sparsity_ratio_granularity)
-        prune_vit = keep["vit"] is not None and float(keep["vit"]) < 1.
-        prune_llm = keep["llm"] is not None and float(keep["llm"]) < 1.
-        self.vit_dense, self.llm_dense = prune_vit, prune_llm
+        pruned = {part: ratio is not None and (not lora_model or float(ratio) < 1.) for part, ratio in keep.items()}
+        if lora_model:
+            self.vit_dense, self.llm_dense = pruned["vit"], pruned["llm"]
 
-        def tower(cls, module_to_process, model_prefix, ratio):
-            sd = global_sparsity_dict if global_sparsity_dict is not None else self.get_sparsity(1 - ratio, None)
-            self.model = cls._prune(self, self.model, self.data_loader, device, model_prefix=model_prefix,
-                                    module_to_process=module_to_process, n_samples=self.num_samples, sparsity_ratio=sd,
-                                    lora_model=True)
-            self._done_towers = getattr(self, "_done_towers", []) + [module_to_process]
-
-        if prune_vit:
-            tower(VITLayerSparseGPTPruner, f"{self.vit_model_prefix}.blocks", self.vit_model_prefix, keep["vit"])
-        if prune_llm:
-            if "t5_model" in self.t5_model_prefix:
-                for side in ("encoder", "decoder"):
-                    tower(T5LayerSparseGPTPruner, f"{self.t5_model_prefix}.{side}.block", self.t5_model_prefix, keep["llm"])
-            else:
-                tower(T5LayerSparseGPTPruner, self._llm_layers(), self.t5_model_prefix, keep["llm"])
+        def own(part):
+            return lambda: global_sparsity_dict if global_sparsity_dict is not None else self.get_sparsity(1 - keep[part], None)
+        self._prune_towers(lora_model, **{part: own(part) if pruned[part] else None for part in keep})
         self.model_reset(self.model, dtype_record, requires_grad_record, device)
         _release_factor_caches()
         return self.model, global_sparsity_dict

@@ -18,6 +18,9 @@ zeroed in place unless `lora_model`).  What differs is where the arithmetic runs
   sort / topk loop / threshold; scatter_; W[mask]=0      8-byte readback per BLOCK
   (:322-341, :670-687)
 
+This module holds the Wanda statistics, the per-block step and the BLIP pruner's gating; the tower step, the tower
+sequence and the constructor keywords it shares with the DSnoT and SparseGPT pruners are in `tower_walk.py`.
+
 There is no CPU fallback: without the HIP library or a GPU model the pruner raises.
 """
 from __future__ import annotations
@@ -27,7 +30,8 @@ import torch
 
 from lavis.common.registry import registry
 from lavis.compression.pruners import calibration as cal
-from lavis.compression.pruners.layer_single_base_pruner import LayerSparsity, LayerWiseBasePruner
+from lavis.compression.pruners.layer_single_base_pruner import LayerSparsity
+from lavis.compression.pruners.tower_walk import TowerKind, TowerPruner, autocast_bf16, autocast_default, input_signature
 from lavis.compression.pruners.utils import print_time
 from vlmc import config, phases
 
@@ -58,7 +62,7 @@ class WandaStatCollector:
             x = inp[0].data
             if x.dim() == 2:
                 x = x.unsqueeze(0)
-            key = (x.data_ptr(), tuple(x.shape), tuple(x.stride()), x.dtype, x._version)
+            key = input_signature(x)
             hit = self._cache.get(key)
             stacked = cal.stacked_samples()          # (samples, batch per sample, sample indices) of a batched replay call
             calls, b0, idx = stacked if stacked and stacked[0] * stacked[1] == x.shape[0] else (1, x.shape[0], (self._cur,))
@@ -170,12 +174,14 @@ def _importance_readback(backlog, owner=None):
     backlog.clear()
 
 
-class _WandaBlockMixin:
-    """Per-block Wanda step shared by the T5/LLM and ViT variants."""
+class _WandaPruner(TowerPruner):
+    """The Wanda tower kinds and per-block step shared by the T5/LLM, ViT and BLIP pruners."""
+    # (ragged text always walks as one padded group: the Wanda statistic takes per-sample token counts, WandaStatCollector)
+    llm_kind = TowerKind(vit=False, tuple_output=True, autocast=autocast_bf16, pad_ragged=lambda: True)
+    vit_kind = TowerKind(vit=True, tuple_output=False, autocast=autocast_default, pad_ragged=None)
 
-    def _wanda_block(self, i, subset, run_pass, n_inps, batch0, *, unstructured_mode, module_to_process, model_prefix,
-                     sparsity_ratio, lora_model):
-        from vlmc import ops, wanda
+    def _block_step(self, i, subset, run_pass, n_inps, batch0, *, kind, module_to_process, model_prefix, sparsity_ratio,
+                    lora_model):
         col = WandaStatCollector(subset)
         try:
             run_pass(col.next_sample, outputs=False)
@@ -184,7 +190,8 @@ class _WandaBlockMixin:
         with phases.phase("stat"):
             stats = col.finalize()
         with phases.phase("select"):
-            self._wanda_select_block(i, subset, stats, n_inps, batch0, unstructured_mode=unstructured_mode,
+            # per-output-row selection in a T5/LLM tower, ONE matrix-wide threshold per linear in the ViT (:670-687)
+            self._wanda_select_block(i, subset, stats, n_inps, batch0, unstructured_mode="matrix" if kind.vit else "row",
                                      module_to_process=module_to_process, model_prefix=model_prefix,
                                      sparsity_ratio=sparsity_ratio, lora_model=lora_model)
 
@@ -220,124 +227,36 @@ class _WandaBlockMixin:
         _importance_backlog(self.__dict__.setdefault("_score_backlog", []), subset, names, partial_rows,
                             [subset[n].weight.numel() for n in names])
 
+    def _end_of_tower(self, walked):
+        if walked:
+            _importance_readback(self.__dict__.setdefault("_score_backlog", []), self)
+
 
 # --------------------------------------------------------------------------------------
 @registry.register_pruner("t5_wanda_pruner")
-class T5LayerWandaPruner(LayerWiseBasePruner, _WandaBlockMixin):
+class T5LayerWandaPruner(_WandaPruner):
     """T5 / OPT / LLaMA tower: per-output-row selection (wanda_pruner.py:84-494)."""
     pruner_name = "t5_wanda_pruner"
+    tower_kind = _WandaPruner.llm_kind
 
-    def __init__(self, model, data_loader, prune_spec=None, importance_scores_cache=None,
-                 keep_indices_or_masks_cache=None, is_strct_pruning=False, num_samples=64, is_global=False,
-                 model_prefix="t5_model", sparsity_ratio_granularity=None, max_sparsity_per_layer=0.8,
-                 score_method="obd_avg", num_data_first_stage=128, num_noise=1, sparsity_dict=None, noise_eps=1e-3,
-                 prune_per_model=False, prune_n=0, prune_m=0, **kwargs):
-        super().__init__(model=model, data_loader=data_loader, prune_spec=prune_spec,
-                         is_strct_pruning=is_strct_pruning, importance_scores_cache=importance_scores_cache,
-                         keep_indices_or_masks_cache=keep_indices_or_masks_cache, is_global=is_global,
-                         num_samples=num_samples, model_prefix=model_prefix,
-                         sparsity_ratio_granularity=sparsity_ratio_granularity,
-                         max_sparsity_per_layer=max_sparsity_per_layer, score_method=score_method,
-                         num_data_first_stage=num_data_first_stage, num_noise=num_noise, sparsity_dict=sparsity_dict,
-                         noise_eps=noise_eps, prune_per_model=prune_per_model, prune_n=prune_n, prune_m=prune_m)
+    def __init__(self, model, data_loader, model_prefix="t5_model", **kwargs):
+        super().__init__(model, data_loader, model_prefix, **kwargs)
 
     def forward_to_cache(self, model, batch, lora_model=False):
         return model(batch)
 
-    def check_sparsity(self, model, module_to_process="encoder.block"):
-        layers = cal.get_module_recursive(model, module_to_process)
-        zeros = total = 0
-        for layer in layers:
-            for mod in cal.find_layers(layer).values():
-                zeros += (mod.weight.data == 0).sum().item()
-                total += mod.weight.numel()
-        return float(zeros) / total
-
-    def prepare_calibration_input_encoder(self, model, dataloader, model_prefix, n_samples,
-                                          module_to_process="encoder.block", lora_model=False):
-        cfg = getattr(model, model_prefix).config
-        use_cache, cfg.use_cache = cfg.use_cache, False
-        try:
-            return cal.capture_block_inputs(model, dataloader, n_samples, module_to_process, self.forward_to_cache,
-                                            lora_model, vit=False, model_prefix=self.model_prefix, done_towers=getattr(self, "_done_towers", None),
-                                        proxy_cache=self.__dict__.setdefault("_proxy_cache", {}))
-        finally:
-            cfg.use_cache = use_cache
-
-    @print_time
-    def _prune(self, model, dataloader, model_prefix, module_to_process="encoder.block", n_samples=64,
-               sparsity_ratio=0.5, lora_model=False):
-        cfg = getattr(model, model_prefix).config
-        use_cache, cfg.use_cache = cfg.use_cache, False
-        with torch.no_grad():
-            inps, outs, caches = self.prepare_calibration_input_encoder(model, dataloader, model_prefix, n_samples,
-                                                                        module_to_process, lora_model)
-        # under calibration sharding every rank holds 1/world of the samples; statistics are global
-        n_inps, batch0 = len(inps) * cal.calibration_shard()[1], inps[0].shape[0]
-
-        def prune_block(i, layer, subset, run_pass, state):
-            self._wanda_block(i, subset, run_pass, n_inps, batch0, unstructured_mode="row",
-                              module_to_process=module_to_process, model_prefix=model_prefix,
-                              sparsity_ratio=sparsity_ratio, lora_model=lora_model)
-
-        cal.walk_blocks(model, inps, outs, caches, module_to_process, n_samples,
-                        lambda: model.maybe_autocast(dtype=torch.bfloat16), prune_block, tuple_output=True,
-                        pad_ragged=True)                       # (the Wanda statistic takes per-sample token counts: WandaStatCollector)
-        _importance_readback(self.__dict__.setdefault("_score_backlog", []), self)
-        cfg.use_cache = use_cache
-        cal.release_tower_memory()
-        return model
-
 
 @registry.register_pruner("vit_wanda_pruner")
-class VITLayerWandaPruner(LayerWiseBasePruner, _WandaBlockMixin):
+class VITLayerWandaPruner(_WandaPruner):
     """EVA ViT tower: ONE matrix-wide threshold per linear (wanda_pruner.py:497-793)."""
     pruner_name = "vit_wanda_pruner"
+    tower_kind = _WandaPruner.vit_kind
 
-    def __init__(self, model, data_loader, prune_spec=None, importance_scores_cache=None,
-                 keep_indices_or_masks_cache=None, is_strct_pruning=False, num_samples=64, is_global=False,
-                 model_prefix="visual", sparsity_ratio_granularity=None, max_sparsity_per_layer=0.8,
-                 score_method="obd_avg", num_data_first_stage=128, num_noise=1, sparsity_dict=None, noise_eps=1e-3,
-                 prune_per_model=False, prune_n=0, prune_m=0, **kwargs):
-        super().__init__(model=model, data_loader=data_loader, prune_spec=prune_spec,
-                         is_strct_pruning=is_strct_pruning, importance_scores_cache=importance_scores_cache,
-                         keep_indices_or_masks_cache=keep_indices_or_masks_cache, is_global=is_global,
-                         num_samples=num_samples, model_prefix=model_prefix,
-                         sparsity_ratio_granularity=sparsity_ratio_granularity,
-                         max_sparsity_per_layer=max_sparsity_per_layer, score_method=score_method,
-                         num_data_first_stage=num_data_first_stage, num_noise=num_noise, sparsity_dict=sparsity_dict,
-                         noise_eps=noise_eps, prune_per_model=prune_per_model, prune_n=prune_n, prune_m=prune_m)
+    def __init__(self, model, data_loader, model_prefix="visual", **kwargs):
+        super().__init__(model, data_loader, model_prefix, **kwargs)
 
     def forward_to_cache(self, model, batch, lora_model=False):
         return model.encode_image(batch["image"])
-
-    check_sparsity = T5LayerWandaPruner.check_sparsity
-
-    def prepare_calibration_input_encoder(self, model, dataloader, model_prefix, n_samples,
-                                          module_to_process="encoder.block", lora_model=False):
-        return cal.capture_block_inputs(model, dataloader, n_samples, module_to_process, self.forward_to_cache,
-                                        lora_model, vit=True, done_towers=getattr(self, "_done_towers", None),
-                                        proxy_cache=self.__dict__.setdefault("_proxy_cache", {}))
-
-    @print_time
-    def _prune(self, model, dataloader, model_prefix, module_to_process="encoder.block", n_samples=64,
-               sparsity_ratio=0.5, lora_model=False):
-        with torch.no_grad():
-            inps, outs, caches = self.prepare_calibration_input_encoder(model, dataloader, model_prefix, n_samples,
-                                                                        module_to_process, lora_model)
-        # under calibration sharding every rank holds 1/world of the samples; statistics are global
-        n_inps, batch0 = len(inps) * cal.calibration_shard()[1], inps[0].shape[0]
-
-        def prune_block(i, layer, subset, run_pass, state):
-            self._wanda_block(i, subset, run_pass, n_inps, batch0, unstructured_mode="matrix",
-                              module_to_process=module_to_process, model_prefix=model_prefix,
-                              sparsity_ratio=sparsity_ratio, lora_model=lora_model)
-
-        cal.walk_blocks(model, inps, outs, caches, module_to_process, n_samples, lambda: model.maybe_autocast(),
-                        prune_block, tuple_output=False, memo_cache=self.__dict__.get("_proxy_cache"))
-        _importance_readback(self.__dict__.setdefault("_score_backlog", []), self)
-        cal.release_tower_memory()
-        return model
 
 
 def layer_to_group_mapping(pruner, granularity):
@@ -378,41 +297,19 @@ def uniform_or_layer_sparsity(pruner, original_sparsity, granularity, loss_func=
 
 
 @registry.register_pruner("blipt5_wanda_pruner")
-class BLIPT5LayerWandaPruner(LayerWiseBasePruner):
+class BLIPT5LayerWandaPruner(_WandaPruner):
     """ViT tower, then T5 encoder, then T5 decoder (or the LLaMA/OPT stack) --
     wanda_pruner.py:796-1052."""
     pruner_name = "blipt5_wanda_pruner"
 
     def __init__(self, model, data_loader, t5_prune_spec=None, vit_prune_spec=None, t5_pruning_method=None,
-                 vit_pruning_method=None, t5_importance_scores_cache=None, t5_keep_indices_or_masks_cache=None,
-                 vit_importance_scores_cache=None, vit_keep_indices_or_masks_cache=None, importance_scores_cache=None,
-                 keep_indices_or_masks_cache=None, is_strct_pruning=False, num_samples=64, is_global=False,
-                 t5_model_prefix="t5_model", vit_model_prefix="visual_encoder", sparsity_ratio_granularity=None,
-                 max_sparsity_per_layer=0.8, score_method="obd_avg", num_data_first_stage=128, num_noise=1,
-                 sparsity_dict=None, noise_eps=1e-3, prune_per_model=False, peft_postfix="", prune_n=0, prune_m=0,
+                 vit_pruning_method=None, t5_model_prefix="t5_model", vit_model_prefix="visual_encoder", peft_postfix="",
                  **kwargs):
-        super().__init__(model=model, data_loader=data_loader, prune_spec=None, is_strct_pruning=is_strct_pruning,
-                         importance_scores_cache=importance_scores_cache,
-                         keep_indices_or_masks_cache=keep_indices_or_masks_cache, is_global=is_global,
-                         num_samples=num_samples, model_prefix=f"{vit_model_prefix}+{t5_model_prefix}",
-                         sparsity_ratio_granularity=sparsity_ratio_granularity,
-                         max_sparsity_per_layer=max_sparsity_per_layer, score_method=score_method,
-                         num_data_first_stage=num_data_first_stage, num_noise=num_noise, sparsity_dict=sparsity_dict,
-                         noise_eps=noise_eps, prune_per_model=prune_per_model, prune_n=prune_n, prune_m=prune_m)
-        self.t5_prune_spec = t5_prune_spec
-        self.vit_prune_spec = vit_prune_spec
-        self.peft_postfix = peft_postfix
+        super().__init__(model, data_loader, f"{vit_model_prefix}+{t5_model_prefix}", **dict(kwargs, prune_spec=None))
         self.vit_dense = True
         self.llm_dense = True
-        assert t5_pruning_method is not None
-        assert vit_pruning_method is not None
-        self.t5_model_prefix = t5_model_prefix
-        self.vit_model_prefix = vit_model_prefix
-
-    # the tower implementations are borrowed as unbound methods, like the reference does with
-    # functools.partial (:983-988, :1011-1015)
-    _wanda_block = _WandaBlockMixin._wanda_block
-    _wanda_select_block = _WandaBlockMixin._wanda_select_block
+        self._set_blip_towers(t5_prune_spec, vit_prune_spec, t5_pruning_method, vit_pruning_method, t5_model_prefix,
+                              vit_model_prefix, peft_postfix)
 
     def get_sparsity(self, original_sparsity, sparsity_ratio_granularity=None):
         return uniform_or_layer_sparsity(self, original_sparsity, sparsity_ratio_granularity)
@@ -421,15 +318,6 @@ class BLIPT5LayerWandaPruner(LayerWiseBasePruner):
         if lora_model:
             return model(batch, vit_dense=self.vit_dense, llm_dense=self.llm_dense)      # :941-945
         return model(batch)
-
-    def _tower(self, cls, last=False, **kw):
-        self.prepare_calibration_input_encoder = lambda *a, **k: cls.prepare_calibration_input_encoder(self, *a, **k)
-        if last:          # nothing is captured after this tower: what a capture phase records for the NEXT one is not recorded
-            self.__dict__.setdefault("_proxy_cache", {})[("last_tower",)] = kw["module_to_process"]
-        out = cls._prune(self, self.model, self.data_loader, **kw)
-        # the finished tower's blocks may replay from HIP graphs while the next tower's inputs are captured
-        self._done_towers = getattr(self, "_done_towers", []) + [kw["module_to_process"]]
-        return out
 
     @cal.quiet_gc
     @print_time
@@ -446,26 +334,16 @@ class BLIPT5LayerWandaPruner(LayerWiseBasePruner):
         self.llm_dense = True if float(t5_keep_ratio) < 1. else False
         self._defer_score_readback = True           # importance scores are read back once, below
         try:
-            prune_t5 = self.t5_prune_spec is not None and float(t5_keep_ratio) < 1.
-            if self.vit_prune_spec is not None and float(vit_keep_ratio) < 1.:
-                sd = global_sparsity_dict if global_sparsity_dict not in [None, "none"] else \
+            def vit_sparsity():
+                return global_sparsity_dict if global_sparsity_dict not in [None, "none"] else \
                     self.get_sparsity(1 - vit_keep_ratio, sparsity_ratio_granularity=None)
-                self.model = self._tower(VITLayerWandaPruner, last=not prune_t5, model_prefix=self.vit_model_prefix,
-                                         module_to_process=f"{self.vit_model_prefix}.blocks",
-                                         n_samples=self.num_samples, sparsity_ratio=sd, lora_model=lora_model)
 
-            if prune_t5:
-                sd = global_sparsity_dict if global_sparsity_dict is not None else \
+            def t5_sparsity():
+                return global_sparsity_dict if global_sparsity_dict is not None else \
                     self.get_sparsity(1 - t5_keep_ratio, sparsity_ratio_granularity=None)
-                if "t5_model" in self.t5_model_prefix:
-                    for side in ("encoder", "decoder"):
-                        self.model = self._tower(T5LayerWandaPruner, last=side == "decoder", model_prefix=self.t5_model_prefix,
-                                                 module_to_process=f"{self.t5_model_prefix}.{side}.block",
-                                                 n_samples=self.num_samples, sparsity_ratio=sd, lora_model=lora_model)
-                else:
-                    self.model = self._tower(T5LayerWandaPruner, last=True, model_prefix=self.t5_model_prefix,
-                                             module_to_process=f"{self.t5_model_prefix}{self.peft_postfix}.model.layers",
-                                             n_samples=self.num_samples, sparsity_ratio=sd, lora_model=lora_model)
+            self._prune_towers(lora_model,
+                               vit=vit_sparsity if self.vit_prune_spec is not None and float(vit_keep_ratio) < 1. else None,
+                               llm=t5_sparsity if self.t5_prune_spec is not None and float(t5_keep_ratio) < 1. else None)
         finally:
             # also when a tower raises: the towers done so far get their importance scores, the flag does not outlive
             # the call (a later stand-alone tower prune on this object reads its scores back itself)
