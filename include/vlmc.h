@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VLMC_ABI_VERSION 23
+#define VLMC_ABI_VERSION 24
 
 #define VLMC_OK 0
 #define VLMC_EINVAL (-1)     /* bad argument (shape, dtype, alignment, null pointer) */
@@ -232,6 +232,21 @@ int vlmc_pack_24(const void *W, int dtype, int64_t out_features, int64_t in_feat
                  void *values, uint8_t *meta, unsigned int *bad_groups, void *stream);
 int vlmc_unpack_24(const void *values, const uint8_t *meta, int dtype, int64_t out_features, int64_t in_features, void *W, int64_t ldw,
                    uint8_t *mask /* NULL or [out, in] */, int64_t ldm, unsigned int *bad_groups, void *stream);
+
+/* ---- a linear on the PACKED weight (inference: the rows of a generation step) ---------------------------------------------------
+ *     Y[m, n] = wd(sum_k X[m, k] * W24[n, k] + bias[n])        W24 = vlmc_unpack_24(values, meta)
+ * bit for bit what vlmc_linear_fwd gives on the unpacked weight (one accumulator per element over the K-steps of 32 in ascending
+ * order on v_mfma_f32_16x16x32, the pruned positions multiplied as the zeros they are), hence batch-invariant like it.  values
+ * [N, K / 2] and meta [N, K / 8] contiguous, as vlmc_pack_24 writes them; K and ldx multiples of 8, X 16-byte aligned; dtype
+ * VLMC_F16 or VLMC_BF16 (VLMC_F32: VLMC_EINVAL); bias [N] in the dtype or NULL.  meta is TRUSTED (two 2-bit indices per group
+ * cannot address outside it; validate once with vlmc_unpack_24's bad_groups).
+ * M <= vlmc_linear_fwd_24_max_rows() (a multiple of 16, >= 16): one kernel that reads the packed bytes once and expands them in
+ * registers; no workspace.  Larger M (prefill): the weight is unpacked into `workspace` (16-byte aligned,
+ * vlmc_linear_fwd_24_workspace() bytes >= N * K * 2 -- one dense weight, reusable for every layer) and the dense kernel runs. */
+int vlmc_linear_fwd_24_max_rows(void);
+size_t vlmc_linear_fwd_24_workspace(int64_t M, int64_t N, int64_t K);
+int vlmc_linear_fwd_24(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
+                       int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- dense calibration forward of one linear (MFMA) ---------------------------------------------
  * Replaces `F.linear(x, weight, bias)` inside the block forwards of the calibration replay,

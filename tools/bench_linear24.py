@@ -1,0 +1,142 @@
+"""The packed 2:4 linear (vlmc_linear_fwd_24) against the dense kernel (vlmc_linear_fwd on the unpacked weight) at the LLM shapes of
+Vicuna-7B and FlanT5-XL, fp16, COLD weights: every timed call takes the next of a pool of weight copies, and a round over the pool
+holds more than twice the 256 MiB Infinity Cache for the packed set and the dense set alike (one packed Vicuna layer is 228 MB
+and would otherwise stay cached while its dense form does not).
+
+Two clocks, both on the device:
+  kernel   the kernel's own begin / end timestamps (vlmc_set_launch_events), summed over a round -- single-kernel routes only
+  graph    a round of calls captured into one HIP graph and replayed between two events: what a stream of such calls costs, kernel
+           gaps included; this is the only clock that sees the two kernels of the unpack route (unpack into scratch + dense)
+Every row is measured `--repeats` times with the routes alternating; the table prints the median and the spread (max - min).
+
+    python tools/bench_linear24.py [--only v7b] [--rows 1,8,16] [--repeats 3] [--out profiles/linear24.md]"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "vlm-compression_amd"), ROOT]
+import torch  # noqa: E402
+
+from vlmc import _lib, ops  # noqa: E402
+
+SHAPES = {"v7b.qkvo": (4096, 4096), "v7b.gate_up": (11008, 4096), "v7b.down": (4096, 11008), "t5.qkvo": (2048, 2048), "t5.wi": (5120, 2048),
+          "t5.wo": (2048, 5120)}
+ROWS = (1, 8, 16, 32, 64, 128, 512, 4096)
+CACHE = 256 << 20
+DEV = "cuda:0"
+
+
+_hipev = None
+
+
+def kernel_us(call, pool):
+    """sum of the kernels' own durations over one round, per call"""
+    global _hipev
+    if _hipev is None:
+        from bench import HipEvents                    # HIP events of the loaded runtime, created through ctypes
+        _hipev = HipEvents()
+    arm = _lib.load().vlmc_set_launch_events
+    evs = [(_hipev.new(), _hipev.new()) for _ in range(pool)]
+    for i, (a, b) in enumerate(evs):
+        arm(a, b)
+        call(i)
+    torch.cuda.synchronize()
+    total = sum(_hipev.elapsed_ms(a, b) for a, b in evs)
+    for a, b in evs:
+        _hipev.free(a, b)
+    return total / pool * 1e3
+
+
+def make_graph(call, pool):
+    g = torch.cuda.CUDAGraph()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for i in range(pool):
+            call(i)                                    # warm: code objects, the scratch weight
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    with torch.cuda.graph(g):
+        for i in range(pool):
+            call(i)
+    return g
+
+
+def graph_us(g, pool):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    g.replay()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / pool * 1e3
+
+
+def med_spread(v):
+    return statistics.median(v), max(v) - min(v)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", default="")
+    ap.add_argument("--rows", default=",".join(map(str, ROWS)))
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_linear24.py measures on the GPU only"
+    rows = [int(r) for r in args.rows.split(",")]
+    max_rows = ops.linear_fwd_24_max_rows()
+    lines = [f"max_rows of this build: {max_rows}; fp16; median of {args.repeats} (spread = max - min); GB/s = weight bytes of the route / kernel time",
+             "",
+             "| shape (N x K) | M | packed kernel us (spread) | GB/s | dense kernel us (spread) | GB/s | packed / dense | "
+             "graph: packed entry us | graph: unpack route us | graph: dense us |",
+             "|---|---|---|---|---|---|---|---|---|---|"]
+    print("\n".join(lines), flush=True)
+    for name, (N, K) in SHAPES.items():
+        if args.only and args.only not in name:
+            continue
+        g = torch.Generator(device=DEV).manual_seed(0)
+        W = (torch.randn(N, K, device=DEV, generator=g) * 0.02).half()
+        keep, _ = ops.wanda_select(W, torch.rand(K, device=DEV, generator=g) + 0.5, "nm", n=2, m=4)
+        values, meta = ops.pack_24(W, keep)
+        packed_bytes, dense_bytes = values.numel() * 2 + meta.numel(), W.numel() * 2
+        pool = 2 * CACHE // packed_bytes + 1           # a round of the SMALLER set still holds more than twice the cache
+        Vs, Ms, Ws = [values.clone() for _ in range(pool)], [meta.clone() for _ in range(pool)], [W.clone() for _ in range(pool)]
+        del keep
+        for M in rows:
+            x = torch.randn(M, K, device=DEV, generator=g).half()
+            want = ops.linear_fwd(x, W)
+            assert torch.equal(ops.linear_fwd_24(x, values, meta).view(torch.int16), want.view(torch.int16)), (name, M)
+            calls = {"packed": lambda i: ops.linear_fwd_24(x, Vs[i], Ms[i]), "unpack": lambda i: ops.linear_fwd_24(x, Vs[i], Ms[i], unpack=True),
+                     "dense": lambda i: ops.linear_fwd(x, Ws[i])}
+            graphs = {k: make_graph(f, pool) for k, f in calls.items()}
+            t = {k: [] for k in ("k_packed", "k_dense", "g_packed", "g_unpack", "g_dense")}
+            for _ in range(args.repeats):                                   # the routes alternate inside every repeat
+                if M <= max_rows:
+                    t["k_packed"].append(kernel_us(calls["packed"], pool))
+                t["k_dense"].append(kernel_us(calls["dense"], pool))
+                for k in ("packed", "unpack", "dense"):
+                    t["g_" + k].append(graph_us(graphs[k], pool))
+            kd, sd = med_spread(t["k_dense"])
+            if M <= max_rows:
+                kp, sp = med_spread(t["k_packed"])
+                pk = f"{kp:.1f} ({sp:.1f}) | {packed_bytes / kp / 1e3:.0f}"
+                ratio = f"{kp / kd:.2f}"
+            else:
+                pk, ratio = "(unpack route) | -", "-"
+            gp, gu, gd = (med_spread(t["g_" + k]) for k in ("packed", "unpack", "dense"))
+            line = (f"| {name} {N} x {K} | {M} | {pk} | {kd:.1f} ({sd:.1f}) | {dense_bytes / kd / 1e3:.0f} | {ratio} | "
+                    f"{gp[0]:.1f} ({gp[1]:.1f}) | {gu[0]:.1f} ({gu[1]:.1f}) | {gd[0]:.1f} ({gd[1]:.1f}) |")
+            print(line, flush=True)
+            lines.append(line)
+            del graphs
+        del Vs, Ms, Ws
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

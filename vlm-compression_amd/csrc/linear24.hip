@@ -1,0 +1,207 @@
+// A linear whose weight stays in the packed 2:4 format of pack24.hip (values [N, K / 2] + meta [N, K / 8], 9 / 16 of the dense
+// bytes), for the few rows of X a generation step brings (rows = batch x beams): there a linear costs the bytes of its weight.
+//
+//   Y[m][n] = wd(sum_k X[m][k] * W24[n][k] + bias[n])        W24 = unpack_24(values, meta)
+//
+// BIT FOR BIT what vlmc_linear_fwd gives on the unpacked weight, because an output element is accumulated exactly as in
+// gemm_nt.hip: W rows are the A operand and X rows the B operand of v_mfma_f32_16x16x32_{f16,bf16}, a lane holds row lane & 15 and
+// k = 8 * (lane >> 4) + j, ONE accumulator per element takes the K-steps of 32 in ascending order (missing chunks of the last
+// step are zeros in both operands), the bias is added in fp32 after the last step, one rounding.  The pruned positions are real
+// zeros in the A fragment and are multiplied like any other weight: an inf in X at a pruned column gives the NaN the dense
+// layer gives.
+//
+// A lane's eight k of a K-step are one pack chunk -- 8 bytes of values and one byte of meta -- so the A fragment is expanded
+// lane-locally in registers and W never touches LDS; the B fragment is 16 contiguous bytes of a row of X (L2-resident: every
+// workgroup reads all of X).  A workgroup owns 16 output features over all of K and keeps ceil(M / 16) accumulator tiles, so
+// the packed weight is read from memory once whatever M is.
+//
+// One dependent MFMA chain per tile would leave one wave's loads in flight per 16 features.  The chain is therefore CARRIED
+// round the workgroup's sixteen waves: K is cut into batches of D steps, batch b belongs to wave b % 16, and a wave starts its
+// batch from the accumulators the previous batch's wave left in LDS (a turn counter in LDS orders them).  The moment a wave has
+// handed on it issues the loads of its next batch, which are in flight while the other fifteen take their turns; the A
+// fragments are expanded before the wave waits for its turn.  Same MFMAs, same order, same accumulator values as one chain:
+// the same bits.
+//
+// M > vlmc_linear_fwd_24_max_rows() (prefill, the vision tower): compute-bound, so the entry point unpacks into the caller's
+// workspace (unpack24_kernel) and runs the dense launch -- the same bits by construction.
+#include "common.hpp"
+#include "mfma.hpp"
+
+// rows of X the packed kernel takes: chosen from tools/bench_linear24.py (profiles/linear24.md); a multiple of 16 in 16..64
+#ifndef VLMC_LINEAR24_MAX_ROWS
+#define VLMC_LINEAR24_MAX_ROWS 64
+#endif
+static_assert(VLMC_LINEAR24_MAX_ROWS % 16 == 0 && VLMC_LINEAR24_MAX_ROWS >= 16 && VLMC_LINEAR24_MAX_ROWS <= 64, "16, 32, 48 or 64");
+
+namespace vlmc {
+
+constexpr int L24_WAVES = 16;
+
+struct Linear24Args {
+    const uint16_t *X;            // [M, K], row stride ldx
+    const uint16_t *values;       // [N, K / 2]
+    const uint8_t *meta;          // [N, K / 8]
+    const uint16_t *bias;         // [N] or NULL
+    uint16_t *Y;                  // [M, N], row stride ldy
+    int64_t ldx, ldy;
+    int M, N, K;
+};
+
+// one pack chunk -> the 8 weights of the A fragment.  Per group of four: code = i0 | i1 << 2 (i0 < i1), the two kept values go
+// to positions i0 and i1, the others are +0.  Two 2-bit indices cannot address outside their group.
+__device__ __forceinline__ u32x4_t expand24(const u32x2_t v, const uint32_t code) {
+    u32x4_t w;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const uint32_t c = code >> (4 * g);
+        const uint64_t lo = uint64_t(v[g] & 0xffffu) << (16 * (c & 3u)), hi = uint64_t(v[g] >> 16) << (16 * ((c >> 2) & 3u));
+        const uint64_t grp = lo | hi;
+        w[2 * g] = uint32_t(grp), w[2 * g + 1] = uint32_t(grp >> 32);
+    }
+    return w;
+}
+
+// MT tiles of 16 rows of X; D K-steps per batch (what a wave holds in registers)
+template <typename T, int MT>
+__global__ __launch_bounds__(64 * L24_WAVES) void linear24_kernel(const Linear24Args a) {
+    constexpr int D = MT == 1 ? 8 : (MT == 2 ? 4 : 2);
+    __shared__ f32x4_t carry[MT][64];
+    __shared__ int turn;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fq = lane >> 4;             // fragment: row (lane & 15), k = 8 * (lane >> 4) + j
+    const int n0 = blockIdx.x * 16;
+    const int chunks = a.K >> 3, nb = (chunks + 4 * D - 1) / (4 * D);
+    if (tid == 0) turn = 0;
+    __syncthreads();
+
+    // rows past the end are clamped to the last one: their products are never stored
+    const int wrow = min(n0 + fr, a.N - 1);
+    const uint16_t *vrow = a.values + int64_t(wrow) * (a.K >> 1);
+    const uint8_t *mrow = a.meta + int64_t(wrow) * chunks;
+    const uint16_t *xrow[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) xrow[t] = a.X + int64_t(min(t * 16 + fr, a.M - 1)) * a.ldx;
+    const int nl = n0 + fq * 4;                            // this lane's four output features
+    // (clamped and never branched round, so that nothing waits for them before the epilogue: without a bias four weights are
+    // loaded in its place and ignored)
+    const uint16_t *bsrc = a.bias != nullptr ? a.bias : a.values;
+    uint16_t braw[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) braw[r] = bsrc[min(nl + r, a.N - 1)];
+
+    struct Batch {
+        u32x2_t v[D];
+        uint32_t code[D];
+        u32x4_t x[MT][D];
+    };
+    // every load is issued whatever the chunk: one past K reads chunk 0 and is zeroed when used (no branch round a load)
+    auto load = [&](int b, Batch &B) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const int c = (b * D + d) * 4 + fq, cc = c < chunks ? c : 0;
+            B.v[d] = *reinterpret_cast<const u32x2_t *>(vrow + cc * 4);
+            B.code[d] = mrow[cc];
+#pragma unroll
+            for (int t = 0; t < MT; ++t) B.x[t][d] = *reinterpret_cast<const u32x4_t *>(xrow[t] + cc * 8);
+        }
+    };
+
+    Batch cur;
+    load(min(wave, nb - 1), cur);
+    for (int b = wave; b < nb; b += L24_WAVES) {
+        const u32x4_t zero = {0u, 0u, 0u, 0u};
+        u32x4_t wf[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const bool ok = (b * D + d) * 4 + fq < chunks;
+            wf[d] = ok ? expand24(cur.v[d], cur.code[d]) : zero;
+#pragma unroll
+            for (int t = 0; t < MT; ++t) cur.x[t][d] = ok ? cur.x[t][d] : zero;
+        }
+        // ---- this wave's turn: the chain so far, D more steps, hand on ------------------------------------------------
+        while (__hip_atomic_load(&turn, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != b) __builtin_amdgcn_s_sleep(1);
+        f32x4_t acc[MT];
+#pragma unroll
+        for (int t = 0; t < MT; ++t) acc[t] = b == 0 ? f32x4_t{0.f, 0.f, 0.f, 0.f} : carry[t][lane];
+#pragma unroll
+        for (int d = 0; d < D; ++d)
+#pragma unroll
+            for (int t = 0; t < MT; ++t) acc[t] = mfma16<T>(wf[d], cur.x[t][d], acc[t]);
+        if (b + 1 < nb) {
+#pragma unroll
+            for (int t = 0; t < MT; ++t) carry[t][lane] = acc[t];
+            __hip_atomic_store(&turn, b + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            load(min(b + L24_WAVES, nb - 1), cur);        // in flight while the other fifteen waves take their turns
+            continue;
+        }
+        // accumulator register r of a lane: feature nl + r (the A row), row t * 16 + fr of X (the B column)
+        const bool vec_ok = (a.ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(a.Y) & 7u) == 0;
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+            const int m = t * 16 + fr;
+            if (m >= a.M || nl >= a.N) continue;
+            uint16_t o[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[r] = from_f32<T>(a.bias != nullptr ? acc[t][r] + to_f32<T>(braw[r]) : acc[t][r]);
+            uint16_t *dst = a.Y + int64_t(m) * a.ldy + nl;
+            if (vec_ok && nl + 3 < a.N) {
+                const u32x2_t v = {uint32_t(o[0]) | uint32_t(o[1]) << 16, uint32_t(o[2]) | uint32_t(o[3]) << 16};
+                *reinterpret_cast<u32x2_t *>(dst) = v;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (nl + r < a.N) dst[r] = o[r];
+            }
+        }
+    }
+}
+
+template <typename T> static void launch_linear24(const Linear24Args &a, hipStream_t s) {
+    const dim3 grid(unsigned((a.N + 15) / 16)), block(64 * L24_WAVES);
+    switch ((a.M + 15) / 16) {
+        case 1: VLMC_LAUNCH_TIMED((linear24_kernel<T, 1>), grid, block, s, a); break;
+        case 2: VLMC_LAUNCH_TIMED((linear24_kernel<T, 2>), grid, block, s, a); break;
+        case 3: VLMC_LAUNCH_TIMED((linear24_kernel<T, 3>), grid, block, s, a); break;
+        default: VLMC_LAUNCH_TIMED((linear24_kernel<T, 4>), grid, block, s, a); break;
+    }
+}
+
+// the dense weight, then 16 bytes for the unpack kernel's bad-group counter (never read: meta is trusted here)
+static size_t linear24_dense_bytes(int64_t N, int64_t K) { return round_up(size_t(N) * size_t(K) * 2, 16); }
+
+}  // namespace vlmc
+
+using namespace vlmc;
+
+extern "C" int vlmc_linear_fwd_24_max_rows(void) { return VLMC_LINEAR24_MAX_ROWS; }
+
+extern "C" size_t vlmc_linear_fwd_24_workspace(int64_t M, int64_t N, int64_t K) {
+    if (M <= VLMC_LINEAR24_MAX_ROWS || N <= 0 || K <= 0) return 0;
+    return linear24_dense_bytes(N, K) + 16;
+}
+
+extern "C" int vlmc_linear_fwd_24(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
+                                  int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream) {
+    VLMC_REQUIRE(dtype == VLMC_F16 || dtype == VLMC_BF16, "vlmc_linear_fwd_24: dtype must be VLMC_F16 or VLMC_BF16");
+    VLMC_REQUIRE(X && values && meta && Y, "vlmc_linear_fwd_24: null pointer");
+    VLMC_REQUIRE(M > 0 && N > 0 && K > 0 && M < (int64_t(1) << 31) && N < (int64_t(1) << 31) && K < (int64_t(1) << 31),
+                 "vlmc_linear_fwd_24: bad shape");
+    VLMC_REQUIRE(K % 8 == 0 && ldx % 8 == 0 && ldx >= K && ldy >= N,
+                 "vlmc_linear_fwd_24: K and the row stride of X must be multiples of 8 elements, ldx >= K, ldy >= N");
+    VLMC_REQUIRE(aligned16(X) && (reinterpret_cast<uintptr_t>(values) & 7u) == 0, "vlmc_linear_fwd_24: X must be 16-byte, values 8-byte aligned");
+    if (M > VLMC_LINEAR24_MAX_ROWS) {
+        const size_t dense = linear24_dense_bytes(N, K);
+        VLMC_REQUIRE(workspace != nullptr && workspace_bytes >= dense + 16 && aligned16(workspace),
+                     "vlmc_linear_fwd_24: M > %d needs a 16-byte aligned workspace of vlmc_linear_fwd_24_workspace() bytes", VLMC_LINEAR24_MAX_ROWS);
+        unsigned int *bad = reinterpret_cast<unsigned int *>(static_cast<unsigned char *>(workspace) + dense);
+        const int rc = vlmc_unpack_24(values, meta, dtype, N, K, workspace, K, nullptr, 0, bad, stream);
+        if (rc != VLMC_OK) return rc;
+        return vlmc_linear_fwd(X, workspace, bias, dtype, M, N, K, ldx, K, Y, ldy, stream);
+    }
+    const Linear24Args a{static_cast<const uint16_t *>(X), static_cast<const uint16_t *>(values), meta, static_cast<const uint16_t *>(bias),
+                         static_cast<uint16_t *>(Y), ldx, ldy, int(M), int(N), int(K)};
+    if (dtype == VLMC_BF16) launch_linear24<bf16_t>(a, as_stream(stream));
+    else launch_linear24<f16_t>(a, as_stream(stream));
+    VLMC_HIP_CHECK_LAUNCH("vlmc_linear_fwd_24");
+    return VLMC_OK;
+}

@@ -151,3 +151,30 @@ def unpack_state_dict_24(state: dict, device=None) -> dict:
         elif not k.endswith("." + PACKED_META):
             out.setdefault(k, v)
     return out
+
+
+def load_packed_24(model, packed_state: dict, strict: bool = True):
+    """Load what `pack_state_dict_24` made into a dense model: exactly the modules whose `<name>.weight_packed24` key is in
+    `packed_state` become `packed24.Linear24` (on the device of the module they replace), then `model.load_state_dict`.  Each
+    `weight_meta24` is validated once here (the kernels trust it); `mask` entries of packed linears (`keep_masks=True`) are
+    recoverable from the metadata and dropped.  Afterwards `model.state_dict()` is the packed state: it goes through
+    `unpack_state_dict_24` / `pack_state_dict_24` bit for bit.  Returns `load_state_dict`'s result."""
+    from . import packed24
+    state = dict(packed_state)
+    for k in [k for k in state if k.endswith("." + PACKED_VALUES)]:
+        name = k[:-len(PACKED_VALUES) - 1]
+        values, meta = state[k], state.get(name + "." + PACKED_META)
+        if meta is None:
+            raise KeyError(f"load_packed_24: {name}.{PACKED_META} is missing")
+        if not packed24.meta_24_is_valid(meta):
+            raise ValueError(f"load_packed_24: {name}.{PACKED_META} holds codes that pack_24 never writes")
+        old = model.get_submodule(name)
+        dev = next((t.device for t in list(old.parameters(recurse=False)) + list(old.buffers(recurse=False))), values.device)
+        bias = state.get(name + ".bias")
+        new = packed24.Linear24(torch.empty_like(values, device=dev), torch.empty_like(meta, device=dev),
+                                None if bias is None else torch.empty_like(bias, device=dev))
+        new.train(old.training)
+        parent, _, child = name.rpartition(".")
+        setattr(model.get_submodule(parent) if parent else model, child, new)
+        state.pop(name + ".mask", None)
+    return model.load_state_dict(state, strict=strict)

@@ -691,6 +691,57 @@ def unpack_24(values: torch.Tensor, meta: torch.Tensor, want_mask: bool = True):
     return w, mask
 
 
+_linear24_ws = Workspace()        # the dense weight of the unpack route: grows to the largest one seen, shared by every layer
+
+
+def linear_fwd_24_max_rows() -> int:
+    """Most rows of x the packed kernel itself takes (vlmc_linear_fwd_24_max_rows); above, `linear_fwd_24` unpacks into scratch."""
+    return int(_lib.load().vlmc_linear_fwd_24_max_rows())
+
+
+def linear_fwd_24_supported(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None) -> bool:
+    """Whether `linear_fwd_24` takes this call: 16-bit x [.., K] and contiguous values [N, K / 2] of one dtype, meta [N, K / 8]
+    uint8 contiguous, all on the GPU, K a multiple of 8."""
+    return (x.is_cuda and values.is_cuda and meta.is_cuda and x.dtype == values.dtype and x.dtype in _16BIT and values.dim() == 2
+            and x.dim() >= 1 and x.shape[-1] == 2 * values.shape[1] and values.shape[1] % 4 == 0 and values.shape[1] > 0
+            and meta.dtype == torch.uint8 and meta.shape == (values.shape[0], values.shape[1] // 4)
+            and values.is_contiguous() and meta.is_contiguous()
+            and (bias is None or (bias.is_cuda and bias.dtype == values.dtype and bias.is_contiguous() and bias.shape == (values.shape[0],))))
+
+
+def linear_fwd_24(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None,
+                  unpack: bool = False) -> torch.Tensor:
+    """y = x @ unpack_24(values, meta).T + bias computed FROM the packed weight (vlmc_linear_fwd_24): bit for bit
+    `linear_fwd(x, unpack_24(values, meta)[0], bias)`, any leading dims.  Up to `linear_fwd_24_max_rows()` rows one kernel reads
+    the packed bytes and expands them in registers; more rows (prefill) unpack into a per-device scratch weight and run the dense
+    kernel.  `meta` is trusted (`pack_24` wrote it, or `formats.load_packed_24` validated it).  `unpack`: the unpack route
+    whatever the number of rows (the cross-check of the packed kernel)."""
+    _need_gpu(x, values, meta, bias)
+    if not linear_fwd_24_supported(x, values, meta, bias):
+        raise TypeError("vlmc.linear_fwd_24: fp16/bf16 x [.., K], contiguous values [N, K / 2] of the same dtype, meta [N, K / 8] uint8 "
+                        "(K % 8 == 0) and a contiguous bias [N] of that dtype expected")
+    N, K = values.shape[0], 2 * values.shape[1]
+    x2 = x.reshape(-1, K)
+    if x2.stride(1) != 1 or x2.stride(0) % 8 != 0 or x2.stride(0) < K or x2.data_ptr() % 16 != 0:
+        x2 = x2.contiguous()
+    M = x2.shape[0]
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    if M == 0:
+        return y.reshape(*x.shape[:-1], N)
+    lib, dt, bptr = _lib.load(), _DT[values.dtype], bias.data_ptr() if bias is not None else None
+    if unpack:
+        dense = (N * K * 2 + 15) // 16 * 16
+        ws = _linear24_ws.get(dense + 16, x.device)        # (the last 16 bytes: the unpack kernel's bad-group counter, unused)
+        _lib.check(lib.vlmc_unpack_24(values.data_ptr(), meta.data_ptr(), dt, N, K, ws.data_ptr(), K, None, 0, ws.data_ptr() + dense, _stream()))
+        _lib.check(lib.vlmc_linear_fwd(x2.data_ptr(), ws.data_ptr(), bptr, dt, M, N, K, x2.stride(0), K, y.data_ptr(), N, _stream()))
+        return y.reshape(*x.shape[:-1], N)
+    nbytes = int(lib.vlmc_linear_fwd_24_workspace(M, N, K))
+    ws = _linear24_ws.get(nbytes, x.device) if nbytes else None
+    _lib.check(lib.vlmc_linear_fwd_24(x2.data_ptr(), values.data_ptr(), meta.data_ptr(), bptr, dt, M, N, K, x2.stride(0), y.data_ptr(), N,
+                                      ws.data_ptr() if ws is not None else None, nbytes, _stream()))
+    return y.reshape(*x.shape[:-1], N)
+
+
 def hessian_accum(H: torch.Tensor, x: torch.Tensor, alpha: float, beta: float, rows=None) -> torch.Tensor:
     """H = alpha * H + beta * x^T x on the tiles on and below the diagonal (SparseGPT.add_batch, sparsegpt_pruner.py:76-79,
     with alpha = n/(n+b) and beta = 2/(n+b)); x [rows, in] fp16 / bf16 / fp32.  `symmetrize_lower(H)` completes H.
