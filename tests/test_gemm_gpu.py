@@ -118,8 +118,8 @@ def test_linear_fwd_group_gives_every_job_the_bits_of_its_own_launch(dtype, M, N
                                          (torch.float16, 128 * 257, 1408, 6144),      # fc2: 5.5 panels x 128.5 blocks
                                          (torch.bfloat16, 8192, 2048, 5120)])         # T5 wo: 256 tiles, K = 5120
 def test_persistent_256x256_kernel_against_fp64_at_prune_size(dtype, M, N, K):
-    """The kernel that carries a prune's GPU time -- gemm_nt_pingpong_kernel on 256 x 256 tiles, persistent workgroups,
-    half panels / half blocks handed out last -- held DIRECTLY against float64 at the calibration replay's own sizes
+    """The kernel that carries a prune's GPU time -- gemm_nt_wide_kernel (all three shapes have K % 64 == 0) on 256 x 256 tiles,
+    persistent workgroups, half panels / half blocks handed out last -- held DIRECTLY against float64 at the calibration replay's own sizes
     (128 samples per launch): 16 384 sampled entries plus the whole last rows / columns (the edge tiles), the stated
     tolerance of test_linear_fwd_matches_fp64_reference."""
     from vlmc import ops
@@ -325,6 +325,69 @@ torch.save(outs, sys.argv[1])
     for extra, other in zip(envs[1:], results[1:]):
         for a, b in zip(results[0], other):
             assert torch.equal(a, b), extra
+
+
+def test_256x256_kernels_agree_on_the_shortest_k_loops(tmp_path):
+    """The prologue, tail and tile hand-off of the 256 x 256 kernels at the K extents where they are all there is: K = 32 (a
+    one-step ring), 64 (one double step), 96 (NSLOT - 1 steps, no steady state), 128 and 192 (two and three double steps), 160
+    (steady state and tail on the half-line kernel).  M = 600, N = 1100 is 2 full + 1 half block of rows and 4 full + 1 half
+    panel -- 15 tiles, more than the 8 below which half panels are scheduled like full ones, so edge tiles are dealt; the
+    Hessians of x [40, 1100] and [100, 1100] are SYRKs on 15 triangle tiles with one and two double steps.  Every variant --
+    whole-line persistent (the default), half-line persistent, lockstep, one workgroup per tile, edges scheduled like full
+    tiles -- has the bits of the register-staged kernel, and the default is within the fp64 bound of
+    test_linear_fwd_matches_fp64_reference.  The switches are read once per process, hence the child processes."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = f"""
+import sys, torch
+sys.path.insert(0, {os.path.join(root, 'vlm-compression_amd')!r})
+from vlmc import ops
+g = torch.Generator(device='cuda:0').manual_seed(23)
+out = []
+for dt in (torch.bfloat16, torch.float16):
+    for K in (32, 64, 96, 128, 160, 192):
+        x = (torch.randn(600, K, generator=g, device='cuda:0') * 0.5 + 0.1).to(dt)
+        w = (torch.randn(1100, K, generator=g, device='cuda:0') * 0.05).to(dt)
+        b = (torch.randn(1100, generator=g, device='cuda:0') * 0.1).to(dt)
+        out.append(dict(kind='linear', x=x.cpu(), w=w.cpu(), b=b.cpu(), y=ops.linear_fwd(x, w, b).cpu()))
+    for T in (40, 100):
+        x = (torch.randn(T, 1100, generator=g, device='cuda:0') * 0.5 + 0.1).to(dt)
+        H = torch.zeros(1100, 1100, device='cuda:0')
+        ops.hessian_accum(H, x, 0.0, 0.01)
+        out.append(dict(kind='hessian', x=x.cpu(), y=ops.symmetrize_lower(H).cpu()))
+torch.save(out, sys.argv[1])
+"""
+    variants = [dict(), dict(VLMC_GEMM_WIDE="0"), dict(VLMC_GEMM_PINGPONG="0"), dict(VLMC_GEMM_PERSIST="0"), dict(VLMC_GEMM_EDGE="0"),
+                dict(VLMC_GEMM_RING="0")]                                 # the last: the register-staged kernel, the reference
+    results = []
+    for i, extra in enumerate(variants):
+        out = tmp_path / f"variant{i}.pt"
+        r = subprocess.run([sys.executable, "-c", code, str(out)], env=dict(os.environ, VLMC_GEMM_BIG_TILES="1", **extra),
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (extra, r.stderr[-2000:])
+        results.append(torch.load(out))
+    ref = results[-1]
+    for extra, res in zip(variants[:-1], results[:-1]):
+        for i, (a, b) in enumerate(zip(res, ref)):
+            assert torch.equal(a["x"], b["x"])                            # (same inputs in every child)
+            assert torch.equal(a["y"], b["y"]), (extra, i, a["kind"], tuple(a["x"].shape), a["x"].dtype)
+    for case in results[0]:
+        x, y = case["x"].double(), case["y"].double()
+        if case["kind"] == "linear":
+            w, b, dtype, K = case["w"].double(), case["b"].double(), case["x"].dtype, x.shape[1]
+            want = x @ w.t() + b
+            scale = x.abs() @ w.abs().t() + b.abs()
+            bound = ULP[dtype] * want.abs() + 4e-7 * math.sqrt(K) * scale + 1e-30
+        else:
+            # products of two 16-bit values are exact in fp32; what rounds, by at most 2^-24 relative each, are the T additions,
+            # beta as an fp32 number and the multiplication by it
+            T = x.shape[0]
+            want = 0.01 * (x.t() @ x)
+            bound = (T + 2) * 2.0 ** -24 * 0.01 * (x.abs().t() @ x.abs()) + 1e-30
+        err = (y - want).abs()
+        assert bool((err <= bound).all()), (case["kind"], tuple(x.shape), float((err / bound).max()))
 
 
 # ---- vlmc_linear_fwd_rows: the dense calibration forward of a PADDED group of ragged samples (round 6) ------------------------------

@@ -24,6 +24,7 @@
 // a fixed order; keys masked at the dtype's minimum behind a row's live keys contribute exact zeros.
 #pragma once
 #include "common.hpp"
+#include "lds_tiles.hpp"
 #include "mfma.hpp"
 #include "softmax_order.hpp"
 
@@ -53,10 +54,6 @@ struct AttnArgs {
 typedef short af_s16x4_t __attribute__((ext_vector_type(4)));
 
 __device__ __attribute__((aligned(16))) const uint32_t attn_zero_chunk[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void attn_glds16(const void *gptr, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(gptr) : "memory", "m0");
-}
 
 struct __attribute__((packed, aligned(2))) AU16x8 { u32x4_t v; };
 __device__ __forceinline__ u32x4_t attn_load16(const uint16_t *p) { return reinterpret_cast<const AU16x8 *>(p)->v; }
@@ -113,8 +110,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArg
             const bool in = r < Tk && ch * 8 < a.d;
             const void *srck = in ? static_cast<const void *>(Kp + int64_t(r) * a.sk_t + ch * 8) : static_cast<const void *>(attn_zero_chunk);
             const void *srcv = in ? static_cast<const void *>(Vp + int64_t(r) * a.sv_t + ch * 8) : static_cast<const void *>(attn_zero_chunk);
-            attn_glds16(srck, __builtin_amdgcn_readfirstlane(lds_k + base * 16));
-            attn_glds16(srcv, __builtin_amdgcn_readfirstlane(lds_v + base * 16));
+            glds16(srck, __builtin_amdgcn_readfirstlane(lds_k + base * 16));
+            glds16(srcv, __builtin_amdgcn_readfirstlane(lds_v + base * 16));
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {

@@ -26,6 +26,7 @@
 // it lies in memory ([k][n], 16-byte chunks) and read with ds_read_b64_tr_b16, gfx950's transposing LDS read, straight into
 // the MFMA operand layout; VLMC_ATTN_TR=0 transposes while writing LDS instead (same bits, the cross-check).
 #include "common.hpp"
+#include "lds_tiles.hpp"
 #include "mfma.hpp"
 
 #include <cstdlib>
@@ -34,7 +35,8 @@ namespace vlmc {
 namespace {
 
 constexpr int TM = 64, TN = 64, KC = 64, NT_ = 256;
-constexpr int ROWB = KC * 2;                           // 128-byte rows in LDS
+constexpr int ROWB = LDS_ROW_BYTES;                    // 128-byte rows in LDS (row_off / tr_off)
+static_assert(ROWB == KC * 2, "a row is one K chunk");
 
 struct BmmArgs {
     const uint16_t *A, *B;
@@ -59,13 +61,6 @@ __device__ __forceinline__ u32x4_t load_partial(const uint16_t *p, int count) {
     __builtin_memcpy(&v, e, 16);
     return v;
 }
-
-// [rows][64 k] image, 16-byte chunk index XOR-ed with row & 7: the 16-row x 4-chunk fragment reads are conflict-free
-__device__ __forceinline__ int row_off(int row, int ch) { return row * ROWB + ((ch ^ (row & 7)) << 4); }
-// [64 k][64 n] image of the NN operand for the transposing reads: a 32-lane half reads rows q, 8 + q (q = 0..3) of one
-// 16-column block -- chunk pairs XOR-ed with (k & 3) | ((k >> 3) & 1) << 2 put its eight 32-byte pieces on all 64 banks once
-__device__ __forceinline__ int tr_swz(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
-__device__ __forceinline__ int tr_off(int k, int ch) { return k * ROWB + ((ch ^ tr_swz(k)) << 4); }
 
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 

@@ -31,6 +31,7 @@
 //   d1 = wd(B16 A16) ; d2 = wd(d1 s) ; sparse: wd(W + d2) M ; masked: wd(W M + d2)
 //   G16 = wd(dY^T x) ; Gm = wd((G16 [M]) s) ; dA, dB: fp32 sums of exact products, rounded to wd once at the end.
 #include "common.hpp"
+#include "lds_tiles.hpp"
 #include "mfma.hpp"
 
 #include <cstdlib>
@@ -43,7 +44,7 @@ typedef _Float16 h16x4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 h16x2_t __attribute__((ext_vector_type(2)));
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
-constexpr int BP = 128, BK = 64, ROWB = 128;                  // rows of 64 elements = 128 B in every LDS image
+constexpr int BP = 128, BK = 64, ROWB = LDS_ROW_BYTES;                  // rows of 64 elements = 128 B in every LDS image
 constexpr int NTH = 512, TP = 4;                              // 2 (p) x 4 (q) waves of 64 x (BQ / 4); BQ = 256 or 192 rows of Q per tile
 constexpr int P_BYTES = BP * ROWB, NSL = 3;
 constexpr int RP = 16;                                        // padded rank
@@ -81,11 +82,6 @@ struct LoraArgs {
                                   // the generator, 2 full wait at the top of a step, 4 no generator, 8 no W / mask / slab loads, 16 no Q loads
 };
 
-__device__ __forceinline__ int row_off(int row, int ch) { return row * ROWB + ((ch ^ (row & 7)) << 4); }
-// [64 k][64 n] image for the transposing reads (as attn_matmul.hip)
-__device__ __forceinline__ int tr_swz(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
-__device__ __forceinline__ int tr_off(int k, int ch) { return k * ROWB + ((ch ^ tr_swz(k)) << 4); }
-
 template <typename T> __device__ __forceinline__ f32x4_t mfma_x16(const u32x2_t &a, const u32x2_t &b, const f32x4_t &c);
 template <> __device__ __forceinline__ f32x4_t mfma_x16<f16_t>(const u32x2_t &a, const u32x2_t &b, const f32x4_t &c) {
     h16x4_t x, y;
@@ -102,9 +98,6 @@ template <> __device__ __forceinline__ f32x4_t mfma_x16<bf16_t>(const u32x2_t &a
 template <typename T> __device__ __forceinline__ float round16(float v) { return to_f32<T>(from_f32<T>(v)); }
 
 // ---- VMEM the compiler does not see ------------------------------------------------------------------------------------
-__device__ __forceinline__ void glds16(const void *gptr, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(gptr) : "memory", "m0");
-}
 __device__ __forceinline__ void gload16(u32x4_t &v, const void *p) {
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
 }

@@ -25,6 +25,7 @@
 // like vlmc_linear_fwd / vlmc_attn_matmul (a sample's outputs have the same bits alone or in a group of 128).
 #pragma once
 #include "common.hpp"
+#include "lds_tiles.hpp"
 #include "mfma.hpp"
 
 #include <cmath>
@@ -52,11 +53,6 @@ struct SdpaArgs {
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
 __device__ __attribute__((aligned(16))) const uint32_t sdpa_zero_chunk[4] = {0u, 0u, 0u, 0u};      // what padding is "loaded" from
-
-// 64 lanes x 16 B from global memory straight into 1 KiB of LDS at `lds_addr` (wave-uniform), lane l at lds_addr + 16 l
-__device__ __forceinline__ void sdpa_glds16(const void *gptr, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(gptr) : "memory", "m0");
-}
 
 struct __attribute__((packed, aligned(2))) SU16x8 { u32x4_t v; };
 __device__ __forceinline__ u32x4_t sdpa_load16(const uint16_t *p) { return reinterpret_cast<const SU16x8 *>(p)->v; }
@@ -101,8 +97,8 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(const SdpaArgs a) {
             const bool in = !(VLMC_SDPA_DBG & 8) && r < a.Tk && ch * 8 < a.d;     // (rows past the image: r >= rows >= Tk)
             const void *srck = in ? static_cast<const void *>(Kp + int64_t(r) * a.sk_t + ch * 8) : static_cast<const void *>(sdpa_zero_chunk);
             const void *srcv = in ? static_cast<const void *>(Vp + int64_t(r) * a.sv_t + ch * 8) : static_cast<const void *>(sdpa_zero_chunk);
-            sdpa_glds16(srck, __builtin_amdgcn_readfirstlane(lds_k + base * 16));
-            sdpa_glds16(srcv, __builtin_amdgcn_readfirstlane(lds_v + base * 16));
+            glds16(srck, __builtin_amdgcn_readfirstlane(lds_k + base * 16));
+            glds16(srcv, __builtin_amdgcn_readfirstlane(lds_v + base * 16));
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
