@@ -27,6 +27,7 @@
 #include "lds_tiles.hpp"
 #include "mfma.hpp"
 #include "softmax_order.hpp"
+#include "vec_access.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -53,22 +54,13 @@ struct AttnArgs {
 
 typedef short af_s16x4_t __attribute__((ext_vector_type(4)));
 
-__device__ __attribute__((aligned(16))) const uint32_t attn_zero_chunk[4] = {0u, 0u, 0u, 0u};
-
-struct __attribute__((packed, aligned(2))) AU16x8 { u32x4_t v; };
-__device__ __forceinline__ u32x4_t attn_load16(const uint16_t *p) { return reinterpret_cast<const AU16x8 *>(p)->v; }
-struct __attribute__((packed, aligned(2))) AU16x4 { uint32_t lo, hi; };
-
 constexpr int kAttnScratchRow = 80;                        // bytes per query row of the P scratch: 32 keys + 16 B (bank spread)
 constexpr int kAttnScratch = 16 * kAttnScratchRow;         // per wave
 
-// the bits of one rounding to the dtype, as an fp32 value again
-template <typename T> __device__ __forceinline__ float attn_round(float v) { return to_f32<T>(from_f32<T>(v)); }
-
 // 4 consecutive addend entries (keys key0 .. key0 + 3 of one query row), zeros past the row's end
-__device__ __forceinline__ AU16x4 attn_bias4(const uint16_t *row, int key0, int Tk, int64_t sk) {
-    AU16x4 r{0u, 0u};
-    if (sk == 1 && key0 + 3 < Tk) return *reinterpret_cast<const AU16x4 *>(row + key0);
+__device__ __forceinline__ U16x4 attn_bias4(const uint16_t *row, int key0, int Tk, int64_t sk) {
+    U16x4 r{0u, 0u};
+    if (sk == 1 && key0 + 3 < Tk) return *reinterpret_cast<const U16x4 *>(row + key0);
     uint16_t e[4] = {0, 0, 0, 0};                                         // (a permuted bias -- T5's [T, T, H] table lookup -- or the row's end)
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -108,8 +100,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArg
         for (int base = wave * 64; base < total; base += NT) {
             const int j = base + lane, r = j / SPR, ch = j - r * SPR;
             const bool in = r < Tk && ch * 8 < a.d;
-            const void *srck = in ? static_cast<const void *>(Kp + int64_t(r) * a.sk_t + ch * 8) : static_cast<const void *>(attn_zero_chunk);
-            const void *srcv = in ? static_cast<const void *>(Vp + int64_t(r) * a.sv_t + ch * 8) : static_cast<const void *>(attn_zero_chunk);
+            const void *srck = in ? static_cast<const void *>(Kp + int64_t(r) * a.sk_t + ch * 8) : static_cast<const void *>(zero_chunk);
+            const void *srcv = in ? static_cast<const void *>(Vp + int64_t(r) * a.sv_t + ch * 8) : static_cast<const void *>(zero_chunk);
             glds16(srck, __builtin_amdgcn_readfirstlane(lds_k + base * 16));
             glds16(srcv, __builtin_amdgcn_readfirstlane(lds_v + base * 16));
         }
@@ -124,8 +116,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArg
             for (int j = 0; j < 8; ++j) {
                 const int i = base + j * NT, r = i / CPR, ch = i - r * CPR;
                 const bool in = i < total && r < Tk && ch * 8 < a.d;
-                kv[j] = in ? attn_load16(Kp + int64_t(r) * a.sk_t + ch * 8) : zero;
-                vv[j] = in ? attn_load16(Vp + int64_t(r) * a.sv_t + ch * 8) : zero;
+                kv[j] = in ? load16_a2(Kp + int64_t(r) * a.sk_t + ch * 8) : zero;
+                vv[j] = in ? load16_a2(Vp + int64_t(r) * a.sv_t + ch * 8) : zero;
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -158,7 +150,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArg
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt) {
                     const int e0 = 16 * dt + 4 * c;
-                    if (e0 < a.d) *reinterpret_cast<AU16x4 *>(orow + e0) = AU16x4{0u, 0u};
+                    if (e0 < a.d) *reinterpret_cast<U16x4 *>(orow + e0) = U16x4{0u, 0u};
                 }
             }
             continue;
@@ -169,10 +161,10 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArg
 #pragma unroll
         for (int ds = 0; ds < DS; ++ds) {
             const int e = 32 * ds + 8 * c;
-            fq[ds] = e < a.d ? attn_load16(Qp + int64_t(qc) * a.sq_t + e) : u32x4_t{0u, 0u, 0u, 0u};
+            fq[ds] = e < a.d ? load16_a2(Qp + int64_t(qc) * a.sq_t + e) : u32x4_t{0u, 0u, 0u, 0u};
         }
         // ---- the addends of this block of queries: requested now, used after the first product ---------------------------
-        AU16x4 b0[NADD >= 1 ? MAXKT : 1], b1[NADD >= 2 ? MAXKT : 1];
+        U16x4 b0[NADD >= 1 ? MAXKT : 1], b1[NADD >= 2 ? MAXKT : 1];
         if constexpr (NADD >= 1) {
             const uint16_t *row = B0p + int64_t(qc) * a.s0_q;
 #pragma unroll
@@ -213,21 +205,21 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArg
             if constexpr (NADD >= 2) __builtin_memcpy(e1, &b1[kt], 8);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                float s = attn_round<T>(acc[kt][g]);
+                float s = round16<T>(acc[kt][g]);
                 if (a.has_mul) {
                     float t = ieee_mul(s, a.mul);
                     asm volatile("" : "+v"(t));                              // (a product of its own: no fused multiply + convert)
-                    s = attn_round<T>(t);
+                    s = round16<T>(t);
                 }
                 if constexpr (NADD >= 1) {
                     float t = ieee_add(s, to_f32<T>(e0[g]));
                     asm volatile("" : "+v"(t));                              // (an fp32 sum of its own, rounded to the dtype afterwards)
-                    s = attn_round<T>(t);
+                    s = round16<T>(t);
                 }
                 if constexpr (NADD >= 2) {
                     float t = ieee_add(s, to_f32<T>(e1[g]));
                     asm volatile("" : "+v"(t));
-                    s = attn_round<T>(t);
+                    s = round16<T>(t);
                 }
                 if constexpr (CLAMP) s = s != s ? s : fmaxf(s, a.clamp_min);  // torch.maximum: NaN stays NaN; -inf becomes the bound
                 s = 16 * kt + 4 * c + g < Tk ? s : ninf;                      // keys of the padding
@@ -305,9 +297,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArg
                 uint16_t e[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) e[g] = q < Tql ? from_f32<T>(oacc[dt][g]) : uint16_t(0);     // (padding queries of a live block: zeros)
-                AU16x4 v;
+                U16x4 v;
                 __builtin_memcpy(&v, e, 8);
-                *reinterpret_cast<AU16x4 *>(orow + e0) = v;
+                *reinterpret_cast<U16x4 *>(orow + e0) = v;
             }
         }
     }

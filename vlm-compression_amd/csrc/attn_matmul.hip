@@ -28,6 +28,7 @@
 #include "common.hpp"
 #include "lds_tiles.hpp"
 #include "mfma.hpp"
+#include "vec_access.hpp"
 
 #include <cstdlib>
 
@@ -47,10 +48,6 @@ struct BmmArgs {
     int nb1, M, N, K;
     int tiles_m, tiles_n, nprob;
 };
-
-struct __attribute__((packed, aligned(2))) U16x8 { u32x4_t v; };
-__device__ __forceinline__ u32x4_t load16_a2(const uint16_t *p) { return reinterpret_cast<const U16x8 *>(p)->v; }
-__device__ __forceinline__ void store16_a2(uint16_t *p, const u32x4_t &v) { reinterpret_cast<U16x8 *>(p)->v = v; }
 
 // up to 8 elements p[0 .. count), the rest zero (the last chunk of a row: nothing past the row's end is touched)
 __device__ __forceinline__ u32x4_t load_partial(const uint16_t *p, int count) {

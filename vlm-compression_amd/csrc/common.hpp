@@ -88,12 +88,6 @@ template <typename T, bool NT = false> __device__ __forceinline__ void store_chu
     }
 }
 
-// Wanda score -> order-preserving unsigned key.  score = |w| * sqrt(s) >= +0 or NaN.
-// NaN sorts last (torch.sort semantics) -> 0xFFFFFFFF; -0 (impossible, but harmless) == +0.
-__device__ __forceinline__ uint32_t score_key(float sc) {
-    return (sc != sc) ? 0xFFFFFFFFu : (__float_as_uint(sc) & 0x7FFFFFFFu);
-}
-
 // Correctly rounded fp32 primitives.  NOTE: HIP's __fsqrt_rn / __fdiv_rn are NOT the IEEE
 // operations (they lower to the approximate native instructions unless OCML rounded ops are
 // enabled); plain sqrtf and `/` are, under -fhip-fp32-correctly-rounded-divide-sqrt (hipcc's
@@ -116,19 +110,7 @@ __device__ __forceinline__ float dsnot_init_metric(int kind, float w, const floa
     return kind == VLMC_DSNOT_INIT_WANDA ? ieee_mul(fabsf(w), sq[c]) : fabsf(w);
 }
 
-constexpr int kWave = 64;
-
-// wave-wide sum of a 32-bit integer (result valid in every lane)
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
+constexpr int kWave = 64;                        // (the wave-wide primitives are in wave_ops.hpp)
 
 // "done once per device" flag for per-device function attributes (the LDS carve-out of a kernel is a property of the
 // function ON a device); thread-safe, one bit per device ordinal.

@@ -21,7 +21,9 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "sort_keys.hpp"
 #include "topk_order.hpp"
+#include "wave_ops.hpp"
 
 namespace vlmc {
 
@@ -128,14 +130,6 @@ __global__ void dsnot_stats_update_kernel(float *__restrict__ scaler, float *__r
 // ------------------------------------------------------------------------------------------
 // refinement
 // ------------------------------------------------------------------------------------------
-// order-preserving key of a signed float for ascending sorts: -0 == +0, NaN last
-__device__ __forceinline__ uint32_t signed_key(float x) {
-    if (x != x) return 0xFFFFFFFFu;
-    x = x + 0.f;                                             // -0 -> +0
-    const uint32_t b = __float_as_uint(x);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 struct Best {          // candidate of an arg-min / arg-max: key, column, payload (D of that column)
     uint32_t key, col;
     float d;
@@ -257,24 +251,13 @@ __global__ __launch_bounds__(64 * NW) void dsnot_simulate_kernel(
         }
     }
     // reconstruction error = sum of D over the pruned columns (fixed tree: lane-sequential, DPP, waves in order)
-    float err;
-    {
-        float v = part;
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));
-        err = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)) +
-              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16)) +
-              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)) +
-              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-        if constexpr (NW > 1) {
-            if (lane == 0) sm.fsum[wave] = err;
-            __syncthreads();
-            err = 0.f;
+    float err = wave_sum_f32_dpp_inorder(part);
+    if constexpr (NW > 1) {
+        if (lane == 0) sm.fsum[wave] = err;
+        __syncthreads();
+        err = 0.f;
 #pragma unroll
-            for (int w = 0; w < NW; ++w) err += sm.fsum[w];
-        }
+        for (int w = 0; w < NW; ++w) err += sm.fsum[w];
     }
     const float sign0 = err > 0.f ? 1.f : (err < 0.f ? -1.f : 0.f);
 
@@ -295,8 +278,8 @@ __global__ __launch_bounds__(64 * NW) void dsnot_simulate_kernel(
                 else if (D[i] > 0.f) posm |= 1u << i;
             }
         }
-        const uint32_t a = wave_sum_u32(uint32_t(__popc(negm))), b = wave_sum_u32(uint32_t(__popc(posm))),
-                       c = wave_sum_u32(uint32_t(__popc(kept_now)));
+        const uint32_t a = wave_sum_u32_shfl(uint32_t(__popc(negm))), b = wave_sum_u32_shfl(uint32_t(__popc(posm))),
+                       c = wave_sum_u32_shfl(uint32_t(__popc(kept_now)));
         NP = a; PP = b; Z = c;
         if constexpr (NW > 1) {
             __syncthreads();

@@ -18,39 +18,11 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "sort_keys.hpp"
 #include "topk_order.hpp"
+#include "wave_ops.hpp"
 
 namespace vlmc {
-
-__device__ __forceinline__ uint32_t dl_signed_key(float x) {          // dsnot.hip: signed_key
-    if (x != x) return 0xFFFFFFFFu;
-    x = x + 0.f;
-    const uint32_t b = __float_as_uint(x);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ uint32_t dl_wave_incl_scan(uint32_t v) {
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x111, 0xF, 0xF, false));   // row_shr:1
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x112, 0xF, 0xF, false));   // row_shr:2
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x114, 0xF, 0xF, false));   // row_shr:4
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x118, 0xF, 0xF, false));   // row_shr:8
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x142, 0xA, 0xF, false));   // row_bcast:15
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x143, 0xC, 0xF, false));   // row_bcast:31
-    return v;
-}
-
-// The compiler otherwise keeps every per-element predicate (a 64-bit lane mask each) and every bin index of one pass alive
-// for the next pass over the same registers: hundreds of spilled SGPRs and 2x the VGPRs (occupancy 1-2 waves per SIMD).  A
-// pass starts from an opaque copy of its mask / range so that what it needs is recomputed (two instructions per element).
-__device__ __forceinline__ uint32_t dl_opaque(uint32_t v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-__device__ __forceinline__ uint32_t dl_uniform(uint32_t v) {          // a wave-uniform value, held in an SGPR
-    v = uint32_t(__builtin_amdgcn_readfirstlane(int(v)));
-    asm volatile("" : "+s"(v));
-    return v;
-}
 
 constexpr int kListCap = 128;        // entries per list = max supported max_cycle
 constexpr int kGroupMax = 8;         // m of n:m
@@ -88,15 +60,6 @@ template <int NW, bool NM> struct ListSmem {
     uint32_t nlist[6];
 };
 
-template <int NW> __device__ __forceinline__ void dl_sync() {
-    if constexpr (NW > 1) __syncthreads();
-    else {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-}
-
 // rank-r (0-based) smallest value of f(i) over the elements with mask bit i; also the count of values below it.
 // f values are < 2^(8*PASSES).  All threads of the workgroup call it with the same r.
 template <int E, int NT, int NW, int PASSES, typename F, typename S, typename R>
@@ -107,7 +70,7 @@ __device__ __forceinline__ uint32_t dl_radix_kth(F f, uint32_t mask, uint32_t r,
     for (int sh = 8 * (PASSES - 1); sh >= 0; sh -= 8) {
         for (int i = tid; i < 256; i += NT) sm.hist[i] = 0;
         dl_sync<NW>();
-        const uint32_t mk = dl_opaque(mask);
+        const uint32_t mk = opaque(mask);
         new_pass();                                                  // (nothing of f is hoisted out of the loop over the passes)
 #pragma unroll
         for (int i = 0; i < E; ++i)
@@ -121,12 +84,12 @@ __device__ __forceinline__ uint32_t dl_radix_kth(F f, uint32_t mask, uint32_t r,
 #pragma unroll
             for (int i = 0; i < 4; ++i) h[i] = sm.hist[tid * 4 + i];
             const uint32_t s = h[0] + h[1] + h[2] + h[3];
-            const uint32_t incl = dl_wave_incl_scan(s);
+            const uint32_t incl = wave_incl_scan_u32_dpp(s);
             const uint32_t lo = incl - s;
             if (lo <= r && r < incl) {
                 uint32_t cum = lo;
                 int i = 0;
-                for (; i < 3; ++i) {
+                for (; i < 3; ++i) {                                 // (walk_bins<4>, written out: the call moves this kernel's code)
                     if (cum + h[i] > r) break;
                     cum += h[i];
                 }
@@ -146,7 +109,7 @@ __device__ __forceinline__ uint32_t dl_radix_kth(F f, uint32_t mask, uint32_t r,
 }
 
 template <int NT, int NW, typename S> __device__ __forceinline__ uint32_t dl_block_sum(uint32_t v, S &sm, int slot) {
-    v = wave_sum_u32(v);
+    v = wave_sum_u32_shfl(v);
     if constexpr (NW > 1) {
         if ((threadIdx.x & 63) == 0) sm.cnt3[slot][threadIdx.x >> 6] = v;
         __syncthreads();
@@ -154,24 +117,6 @@ template <int NT, int NW, typename S> __device__ __forceinline__ uint32_t dl_blo
 #pragma unroll
         for (int w = 0; w < NW; ++w) v += sm.cnt3[slot][w];
         __syncthreads();
-    }
-    return v;
-}
-
-// wave-wide min / max of a 32-bit unsigned (result valid in every lane)
-__device__ __forceinline__ uint32_t dl_wave_min(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const uint32_t o = uint32_t(__shfl_xor(int(v), off, 64));
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t dl_wave_max(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const uint32_t o = uint32_t(__shfl_xor(int(v), off, 64));
-        v = o > v ? o : v;
     }
     return v;
 }
@@ -203,10 +148,10 @@ __device__ __forceinline__ uint32_t dl_extract(const uint32_t (&key)[E], DVal dv
     auto cf = [&](int i) { return (colof(i) ^ flip) & 0x3FFFu; };
     // a pass starts from opaque copies of the direction and the lane's column base: no flipped key or column number of an
     // earlier pass (or, hoisted out of the loop over the lists, of all of them) is kept in a register
-    auto new_pass = [&]() { flip = dl_uniform(flip); tid8 = dl_opaque(tid8); };
+    auto new_pass = [&]() { flip = uniform(flip); tid8 = opaque(tid8); };
     if (fast) {
         uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-        const uint32_t mk0 = dl_opaque(mask);
+        const uint32_t mk0 = opaque(mask);
 #pragma unroll
         for (int i = 0; i < E; ++i) {
             const uint32_t kk = kf(i);
@@ -214,8 +159,8 @@ __device__ __forceinline__ uint32_t dl_extract(const uint32_t (&key)[E], DVal dv
             lo = (in && kk < lo) ? kk : lo;
             hi = (in && kk > hi) ? kk : hi;
         }
-        lo = dl_wave_min(lo);
-        hi = dl_wave_max(hi);
+        lo = wave_min_u32_shfl(lo);
+        hi = wave_max_u32_shfl(hi);
         if constexpr (NW > 1) {
             if ((tid & 63) == 0) { sm.wmin[tid >> 6] = lo; sm.wmax[tid >> 6] = hi; }
             __syncthreads();
@@ -226,12 +171,12 @@ __device__ __forceinline__ uint32_t dl_extract(const uint32_t (&key)[E], DVal dv
                 hi = b > hi ? b : hi;
             }
         }
-        lo = dl_uniform(lo);
-        const uint32_t span = dl_uniform(hi) - lo;                      // (span >> shift) < kFastBins
+        lo = uniform(lo);
+        const uint32_t span = uniform(hi) - lo;                      // (span >> shift) < kFastBins
         uint32_t shift = span < uint32_t(kFastBins) ? 0u : uint32_t(32 - __builtin_clz(span)) - uint32_t(kFastBinsLog2);
         for (int i = tid; i < kFastBins; i += NT) sm.hist[i] = 0;
         dl_sync<NW>();
-        const uint32_t mk1 = dl_opaque(mask);
+        const uint32_t mk1 = opaque(mask);
         new_pass();
 #pragma unroll
         for (int i = 0; i < E; ++i) {                                   // branch-free: the others count into a spare bin of their lane
@@ -239,15 +184,15 @@ __device__ __forceinline__ uint32_t dl_extract(const uint32_t (&key)[E], DVal dv
             atomicAdd(&sm.hist[((mk1 >> i) & 1u) ? bin : uint32_t(kFastBins + 1 + (tid & 63))], 1u);
         }
         dl_sync<NW>();
-        lo = dl_uniform(lo);                                            // (the bins are recomputed in the gather, not kept)
-        shift = dl_uniform(shift);
+        lo = uniform(lo);                                            // (the bins are recomputed in the gather, not kept)
+        shift = uniform(shift);
         if (tid < 64) {                                                 // wave 0: kFastBins / 64 bins per lane
             constexpr int PER = kFastBins / 64;
             uint32_t h[PER];
             uint32_t ssum = 0;
 #pragma unroll
             for (int i = 0; i < PER; ++i) { h[i] = sm.hist[tid * PER + i]; ssum += h[i]; }
-            const uint32_t incl = dl_wave_incl_scan(ssum);
+            const uint32_t incl = wave_incl_scan_u32_dpp(ssum);
             uint32_t cum = incl - ssum;
             const bool mine = cum < n && n <= incl;                     // this lane's bins bring the count to n
             bool found = false;
@@ -267,7 +212,7 @@ __device__ __forceinline__ uint32_t dl_extract(const uint32_t (&key)[E], DVal dv
         if (m <= uint32_t(S::RAWCAP)) {
             // slots are handed out from the END of each bin's range downwards: hist[b] (inclusive prefix) counts down to
             // the bin's start, so afterwards start(b) = hist[b] and end(b) = start(b + 1) = hist[b + 1] (or m at the cut).
-            const uint32_t mk2 = dl_opaque(mask);
+            const uint32_t mk2 = opaque(mask);
             new_pass();
 #pragma unroll
             for (int i = 0; i < E; ++i)
@@ -309,7 +254,7 @@ __device__ __forceinline__ uint32_t dl_extract(const uint32_t (&key)[E], DVal dv
     const uint32_t X = dl_radix_kth<E, NT, NW, 4>(kf, mask, n - 1, sm, c_lt, new_pass);
     // ties with X: all of them, or the (n - c_lt) first by (flipped) column
     uint32_t tie = 0;
-    const uint32_t mk3 = dl_opaque(mask);
+    const uint32_t mk3 = opaque(mask);
     new_pass();
 #pragma unroll
     for (int i = 0; i < E; ++i)
@@ -322,7 +267,7 @@ __device__ __forceinline__ uint32_t dl_extract(const uint32_t (&key)[E], DVal dv
     }
     if (tid == 0) sm.red[2] = 0;
     dl_sync<NW>();
-    const uint32_t mk4 = dl_opaque(mask);
+    const uint32_t mk4 = opaque(mask);
     new_pass();
 #pragma unroll
     for (int i = 0; i < E; ++i)
@@ -399,7 +344,7 @@ __device__ __forceinline__ uint32_t dl_extract_both(const uint32_t (&key)[E], DV
         uint32_t tid8 = uint32_t(tid) * 8u;
         auto colof = [&](int i) { return uint32_t((i / 8) * NT * 8 + (i % 8)) + tid8; };
         uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-        const uint32_t mk0 = dl_opaque(mask);
+        const uint32_t mk0 = opaque(mask);
 #pragma unroll
         for (int i = 0; i < E; ++i) {
             const uint32_t kk = key[i];
@@ -407,8 +352,8 @@ __device__ __forceinline__ uint32_t dl_extract_both(const uint32_t (&key)[E], DV
             lo = (in && kk < lo) ? kk : lo;
             hi = (in && kk > hi) ? kk : hi;
         }
-        lo = dl_wave_min(lo);
-        hi = dl_wave_max(hi);
+        lo = wave_min_u32_shfl(lo);
+        hi = wave_max_u32_shfl(hi);
         if constexpr (NW > 1) {
             if ((tid & 63) == 0) { sm.wmin[tid >> 6] = lo; sm.wmax[tid >> 6] = hi; }
             __syncthreads();
@@ -419,8 +364,8 @@ __device__ __forceinline__ uint32_t dl_extract_both(const uint32_t (&key)[E], DV
                 hi = b > hi ? b : hi;
             }
         }
-        lo = dl_uniform(lo);
-        hi = dl_uniform(hi);
+        lo = uniform(lo);
+        hi = uniform(hi);
         const uint32_t span = hi - lo;
         uint32_t shift = span < uint32_t(kFastBins) ? 0u : uint32_t(32 - __builtin_clz(span)) - uint32_t(kFastBinsLog2);
         const bool win = wlog != 0 && (span >> 1) >= (1u << wlog);        // the two windows do not meet
@@ -435,7 +380,7 @@ __device__ __forceinline__ uint32_t dl_extract_both(const uint32_t (&key)[E], DV
         dl_sync<NW>();
         // `flood_key`: the ONE key half of the elements may share (the regrow keys of all kept columns are G = 0; zero weights have
         // metric 0): counted in a register and added to its bin once per thread.
-        const uint32_t mk1 = dl_opaque(mask);
+        const uint32_t mk1 = opaque(mask);
         uint32_t flood = 0;
 #pragma unroll
         for (int i = 0; i < E; ++i) {
@@ -446,9 +391,9 @@ __device__ __forceinline__ uint32_t dl_extract_both(const uint32_t (&key)[E], DV
         }
         if (flood && binof(flood_key) != kNoBin) atomicAdd(&sm.hist[binof(flood_key)], flood);
         dl_sync<NW>();
-        lo = dl_uniform(lo);
-        hi = dl_uniform(hi);
-        shift = dl_uniform(shift);
+        lo = uniform(lo);
+        hi = uniform(hi);
+        shift = uniform(shift);
         const uint32_t need_d = avail - n;                              // ascending position of the descending list's last entry
         if (tid < 64) {
             constexpr int PER = kFastBins / 64;
@@ -456,7 +401,7 @@ __device__ __forceinline__ uint32_t dl_extract_both(const uint32_t (&key)[E], DV
             uint32_t ssum = 0;
 #pragma unroll
             for (int i = 0; i < PER; ++i) { h[i] = sm.hist[tid * PER + i]; ssum += h[i]; }
-            const uint32_t incl0 = dl_wave_incl_scan(ssum);
+            const uint32_t incl0 = wave_incl_scan_u32_dpp(ssum);
             const uint32_t counted = uint32_t(__builtin_amdgcn_readlane(int(incl0), 63));
             // windowed: the uncounted gap sits between bins 511 and 512 (lanes 31 and 32) of the ascending order
             const uint32_t gap = (win && tid >= 32) ? avail - counted : 0u;
@@ -489,8 +434,8 @@ __device__ __forceinline__ uint32_t dl_extract_both(const uint32_t (&key)[E], DV
         if (ends_ok && m_a <= uint32_t(S::RAWCAP) && m_d <= uint32_t(S::RAWCAP)) {
             // slots are handed out from the END of each bin's range downwards (hist[b] counts down from the inclusive prefix to the
             // bin's start): ascending position p of a candidate; the descending list stores it at avail - 1 - p
-            const uint32_t mk2 = dl_opaque(mask);
-            tid8 = dl_opaque(tid8);
+            const uint32_t mk2 = opaque(mask);
+            tid8 = opaque(tid8);
 #pragma unroll
             for (int i = 0; i < E; ++i)
                 if ((mk2 >> i) & 1u) {
@@ -591,7 +536,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW == 
                     const float v = var_row[col0 + j];
                     g = ieee_div(g, pow_var == 1.f ? v : dl_powf(v, pow_var));
                 }
-                gk[i] = dl_signed_key(g);
+                gk[i] = signed_key(g);
             }
         } else {
 #pragma unroll
@@ -599,25 +544,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW == 
         }
     }
     auto dval = [&](uint32_t col) { return ieee_mul(to_f32<T>(wrow[col]), sum_row[col]); };
-    float err;
-    {
-        float v = part;
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));
-        err = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)) +
-              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16)) +
-              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)) +
-              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-        if constexpr (NW > 1) {
-            if (lane == 0) sm.fsum[wave] = err;
-            __syncthreads();
-            err = 0.f;
+    float err = wave_sum_f32_dpp_inorder(part);                 // (the order of dsnot_simulate_kernel: same sign decision)
+    if constexpr (NW > 1) {
+        if (lane == 0) sm.fsum[wave] = err;
+        __syncthreads();
+        err = 0.f;
 #pragma unroll
-            for (int w = 0; w < NW; ++w) err += sm.fsum[w];
-            __syncthreads();
-        }
+        for (int w = 0; w < NW; ++w) err += sm.fsum[w];
+        __syncthreads();
     }
     const float sign0 = err > 0.f ? 1.f : (err < 0.f ? -1.f : 0.f);
     const uint32_t kept0 = live & ~pruned0;

@@ -33,6 +33,7 @@
 #include "common.hpp"
 #include "lds_tiles.hpp"
 #include "mfma.hpp"
+#include "vec_access.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -95,7 +96,6 @@ template <> __device__ __forceinline__ f32x4_t mfma_x16<bf16_t>(const u32x2_t &a
     __builtin_memcpy(&y, &b, 8);
     return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(x, y, c, 0, 0, 0);
 }
-template <typename T> __device__ __forceinline__ float round16(float v) { return to_f32<T>(from_f32<T>(v)); }
 
 // ---- VMEM the compiler does not see ------------------------------------------------------------------------------------
 __device__ __forceinline__ void gload16(u32x4_t &v, const void *p) {

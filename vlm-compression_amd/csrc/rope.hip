@@ -11,6 +11,7 @@
 // the table is never read: the row is written as zeros and the caller's status word is set (vlmc_rope_status reports it).
 #include "common.hpp"
 #include "mfma.hpp"
+#include "vec_access.hpp"
 
 namespace vlmc {
 
@@ -25,11 +26,9 @@ struct RopeArgs {
     int H, T, d;
 };
 
-struct __attribute__((packed, aligned(2))) RU16x8 { u32x4_t v; };
-
 // 8 elements of a row from element e on
 __device__ __forceinline__ void rope_load8(const uint16_t *p, uint16_t (&e)[8]) {
-    const u32x4_t v = reinterpret_cast<const RU16x8 *>(p)->v;
+    const u32x4_t v = load16_a2(p);
     __builtin_memcpy(e, &v, 16);
 }
 
@@ -96,9 +95,9 @@ template <typename T> __global__ __launch_bounds__(256) void rope_kernel(const R
         }
         u32x4_t v;
         __builtin_memcpy(&v, oq, 16);
-        reinterpret_cast<RU16x8 *>(qo)->v = v;
+        store16_a2(qo, v);
         __builtin_memcpy(&v, ok, 16);
-        reinterpret_cast<RU16x8 *>(ko)->v = v;
+        store16_a2(ko, v);
     }
 }
 

@@ -12,6 +12,7 @@
 #include "common.hpp"
 #include "mfma.hpp"
 #include "softmax_order.hpp"
+#include "wave_ops.hpp"
 
 #include <type_traits>
 
@@ -40,8 +41,7 @@ __global__ __launch_bounds__(256) void row_mean_kernel(const float *__restrict__
         }
         acc = ieee_add(ieee_add(ieee_add(ieee_add(acc, v[0]), v[1]), v[2]), v[3]);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc = ieee_add(acc, __shfl_xor(acc, off, kWave));
+    acc = wave_sum_f32_shfl(acc);
     if (lane == 0) out[row] = ieee_div(acc, float(n));
 }
 
@@ -114,8 +114,7 @@ __global__ __launch_bounds__(256) void rms_norm_kernel(const uint16_t *__restric
         }
         acc = ieee_add(ieee_add(ieee_add(ieee_add(acc, v[0]), v[1]), v[2]), v[3]);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc = ieee_add(acc, __shfl_xor(acc, off, kWave));
+    acc = wave_sum_f32_shfl(acc);
     const float var = ieee_add(ieee_div(acc, float(n)), eps);                   // mean(-1) + eps   (every lane holds the same sum)
     float r;
     if (rsqrt_mode == 0) r = float(1.0 / __builtin_sqrt(double(var)));         // ::rsqrt(float) resolves to the double overload in ATen's HIP build

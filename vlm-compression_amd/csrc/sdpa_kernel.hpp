@@ -27,6 +27,7 @@
 #include "common.hpp"
 #include "lds_tiles.hpp"
 #include "mfma.hpp"
+#include "vec_access.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -51,12 +52,6 @@ struct SdpaArgs {
 };
 
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __attribute__((aligned(16))) const uint32_t sdpa_zero_chunk[4] = {0u, 0u, 0u, 0u};      // what padding is "loaded" from
-
-struct __attribute__((packed, aligned(2))) SU16x8 { u32x4_t v; };
-__device__ __forceinline__ u32x4_t sdpa_load16(const uint16_t *p) { return reinterpret_cast<const SU16x8 *>(p)->v; }
-struct __attribute__((packed, aligned(2))) SU16x4 { uint32_t lo, hi; };
 
 // DS = k-steps of 32 along d (d <= 32 DS), the LDS rows hold 32 DS elements + 16 B
 // MAXKT: 16-key tiles a head may have -- the accumulators of S^T are registers: 16 (18 for 65 <= d <= 96: the ViT's 257 tokens x
@@ -95,8 +90,8 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(const SdpaArgs a) {
         for (int base = hw * 64; base < total; base += wph * 64) {
             const int j = base + lane, r = j / SPR, ch = j - r * SPR;
             const bool in = !(VLMC_SDPA_DBG & 8) && r < a.Tk && ch * 8 < a.d;     // (rows past the image: r >= rows >= Tk)
-            const void *srck = in ? static_cast<const void *>(Kp + int64_t(r) * a.sk_t + ch * 8) : static_cast<const void *>(sdpa_zero_chunk);
-            const void *srcv = in ? static_cast<const void *>(Vp + int64_t(r) * a.sv_t + ch * 8) : static_cast<const void *>(sdpa_zero_chunk);
+            const void *srck = in ? static_cast<const void *>(Kp + int64_t(r) * a.sk_t + ch * 8) : static_cast<const void *>(zero_chunk);
+            const void *srcv = in ? static_cast<const void *>(Vp + int64_t(r) * a.sv_t + ch * 8) : static_cast<const void *>(zero_chunk);
             glds16(srck, __builtin_amdgcn_readfirstlane(lds_k + base * 16));
             glds16(srcv, __builtin_amdgcn_readfirstlane(lds_v + base * 16));
         }
@@ -111,8 +106,8 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(const SdpaArgs a) {
             for (int j = 0; j < 8; ++j) {
                 const int i = base + j * nth, r = i / CPR, ch = i - r * CPR;
                 const bool in = !(VLMC_SDPA_DBG & 8) && i < total && r < a.Tk && ch * 8 < a.d;
-                kv[j] = in ? sdpa_load16(Kp + int64_t(r) * a.sk_t + ch * 8) : zero;
-                vv[j] = in ? sdpa_load16(Vp + int64_t(r) * a.sv_t + ch * 8) : zero;
+                kv[j] = in ? load16_a2(Kp + int64_t(r) * a.sk_t + ch * 8) : zero;
+                vv[j] = in ? load16_a2(Vp + int64_t(r) * a.sv_t + ch * 8) : zero;
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -265,9 +260,9 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(const SdpaArgs a) {
                 uint16_t e[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) e[g] = from_f32<T>(oacc[u][dt][g] * inv[u]);
-                SU16x4 v;                                                     // (d is a multiple of 8: e0 < d means e0 + 3 < d)
+                U16x4 v;                                                     // (d is a multiple of 8: e0 < d means e0 + 3 < d)
                 __builtin_memcpy(&v, e, 8);
-                *reinterpret_cast<SU16x4 *>(orow + e0) = v;
+                *reinterpret_cast<U16x4 *>(orow + e0) = v;
             }
         }
     };
@@ -278,7 +273,7 @@ __global__ __launch_bounds__(256) void sdpa_fwd_kernel(const SdpaArgs a) {
 #pragma unroll
             for (int ds = 0; ds < DS; ++ds) {
                 const int e = 32 * ds + 8 * c;
-                dst[u][ds] = e < a.d ? sdpa_load16(Qp + int64_t(q) * a.sq_t + e) : u32x4_t{0u, 0u, 0u, 0u};
+                dst[u][ds] = e < a.d ? load16_a2(Qp + int64_t(q) * a.sq_t + e) : u32x4_t{0u, 0u, 0u, 0u};
             }
         }
     };

@@ -14,7 +14,10 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "grid_sync.hpp"
+#include "sort_keys.hpp"
 #include "topk_order.hpp"
+#include "wave_ops.hpp"
 
 namespace vlmc {
 
@@ -257,8 +260,8 @@ __global__ __launch_bounds__(256) void sparsegpt_sweep_kernel(float *__restrict_
 // workgroups of the launch agree on the threshold key in three radix levels (11 / 11 / 10 key bits; per level: LDS
 // histogram -> device-scope atomics into the scope's global histogram -> grid barrier -> every workgroup scans the merged
 // bins itself).  Several linears that share a factor are stacked along the rows (vlmc/sparsegpt.py: fasterprune_group);
-// each is a SCOPE with its own rank.  Grid barriers as in wanda_select.hip (matrix_fused_kernel): arrival counters,
-// device-scope atomics only, a bounded wait whose failure is all-or-none -- then nothing has been written, and the last
+// each is a SCOPE with its own rank.  Grid barriers: grid_arrive_wait (grid_sync.hpp) on one arrival counter per level,
+// a bounded wait whose failure is all-or-none -- then nothing has been written, and the last
 // workgroup to finish (done counter) does the whole block alone (thresholds by a streaming radix select, then every row
 // group).  The workspace (kSelWsWords words) must be zero on entry and is returned zero.
 // ------------------------------------------------------------------------------------------
@@ -269,8 +272,6 @@ constexpr int kSelScopes = 4, kSelBins = 2048, kSelLevels = 3;
 constexpr int kSelHistWords = kSelScopes * kSelLevels * kSelBins;
 constexpr int kSelCtl = kSelHistWords;            // [0..2] the levels' barriers, [3] done counter
 constexpr int kSelWsWords = kSelHistWords + 16;
-constexpr uint32_t kSelBarFail = 0x80000000u;
-constexpr uint32_t kSelSpinMax = 1u << 12;        // x (device-scope load + s_sleep, ~2.2 us) ~ 9 ms
 
 struct SelScopes {
     int n;
@@ -279,36 +280,6 @@ struct SelScopes {
     uint32_t rank[kSelScopes];                    // 0-based rank of the threshold among the scope's rows x count scores
 };
 
-__device__ __forceinline__ uint32_t sel_ld_dev(const uint32_t *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// tid 0: arrive and wait for n arrivals; false = the barrier failed (for every workgroup or for none, see wanda_select.hip)
-__device__ __forceinline__ bool sel_arrive_wait(uint32_t *ctr, uint32_t n) {
-    uint32_t v = atomicAdd(ctr, 1u) + 1u;
-    for (uint32_t it = 0;; ++it) {
-        if (v & kSelBarFail) return false;
-        if (v >= n) return true;
-        if (it >= kSelSpinMax) {
-            const uint32_t seen = atomicCAS(ctr, v, v | kSelBarFail);
-            if (seen == v) return false;
-            v = seen;
-            continue;
-        }
-        __builtin_amdgcn_s_sleep(8);
-        v = sel_ld_dev(ctr);
-    }
-}
-
-__device__ __forceinline__ uint32_t sel_wave_incl_scan(uint32_t v) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = uint32_t(__shfl_up(int(v), off, 64));
-        if (int(threadIdx.x & 63) >= off) v += o;
-    }
-    return v;
-}
-
 // 256 threads, PER bins each (thread t holds bins t * PER ..): the bin with cum <= need < cum + h, and cum.
 template <int PER>
 __device__ __forceinline__ void sel_find_rank(const uint32_t (&h)[PER], uint32_t need, uint32_t *red, uint32_t &bin, uint32_t &before) {
@@ -316,7 +287,7 @@ __device__ __forceinline__ void sel_find_rank(const uint32_t (&h)[PER], uint32_t
     uint32_t s = 0;
 #pragma unroll
     for (int i = 0; i < PER; ++i) s += h[i];
-    const uint32_t incl = sel_wave_incl_scan(s);
+    const uint32_t incl = wave_incl_scan_u32_shfl(s);
     if (lane == 63) red[wave] = incl;
     if (tid == 0) { red[8] = 0xFFFFFFFFu; red[9] = 0; }
     __syncthreads();
@@ -325,11 +296,7 @@ __device__ __forceinline__ void sel_find_rank(const uint32_t (&h)[PER], uint32_t
     const uint32_t hi = off + incl, lo = hi - s;
     if (lo <= need && need < hi) {
         uint32_t cum = lo;
-        int i = 0;
-        for (; i < PER - 1; ++i) {
-            if (cum + h[i] > need) break;
-            cum += h[i];
-        }
+        const int i = walk_bins(h, need, cum);
         red[8] = uint32_t(tid * PER + i);
         red[9] = cum;
     }
@@ -501,7 +468,7 @@ __global__ __launch_bounds__(256) void sgpt_select_sweep_kernel(float *__restric
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // my atomics have been performed
         __syncthreads();
 #if !(VLMC_SEL_DBG & 4)
-        if (tid == 0) red[10] = sel_arrive_wait(ws + kSelCtl + lvl, gridDim.x) ? 1u : 0u;
+        if (tid == 0) red[10] = grid_arrive_wait(ws + kSelCtl + lvl, gridDim.x) ? 1u : 0u;
 #else
         if (tid == 0) red[10] = 1;
 #endif
@@ -511,7 +478,7 @@ __global__ __launch_bounds__(256) void sgpt_select_sweep_kernel(float *__restric
         uint32_t h[8];
 #pragma unroll
 #if !(VLMC_SEL_DBG & 8)
-        for (int i = 0; i < 8; ++i) h[i] = sel_ld_dev(&gh[tid * 8 + i]);
+        for (int i = 0; i < 8; ++i) h[i] = ld_dev(&gh[tid * 8 + i]);
 #else
         for (int i = 0; i < 8; ++i) h[i] = lh[tid * 8 + i] + (tid == 0 && i == 0 ? 0x7FFFFFFFu : 0u);
 #endif

@@ -22,56 +22,12 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "grid_sync.hpp"
+#include "sort_keys.hpp"
 #include "topk_order.hpp"
+#include "wave_ops.hpp"
 
 namespace vlmc {
-
-// ------------------------------------------------------------------------------------------
-// wave primitives
-// ------------------------------------------------------------------------------------------
-// Sum over the 64 lanes with DPP (no LDS traffic); result is wave-uniform.
-__device__ __forceinline__ uint32_t wave_sum_u32_dpp(uint32_t v) {
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x141, 0xF, 0xF, true));  // row_half_mirror
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x140, 0xF, 0xF, true));  // row_mirror
-    // every lane of a 16-lane row now holds its row's sum
-    return uint32_t(__builtin_amdgcn_readlane(int(v), 0)) + uint32_t(__builtin_amdgcn_readlane(int(v), 16)) +
-           uint32_t(__builtin_amdgcn_readlane(int(v), 32)) + uint32_t(__builtin_amdgcn_readlane(int(v), 48));
-}
-
-// f32 sum over the 64 lanes with DPP; every lane of the result row holds the total of its 16-lane
-// row, the four row totals are combined through readlane (fixed order => deterministic).
-__device__ __forceinline__ float wave_sum_f32_dpp(float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return (r0 + r1) + (r2 + r3);
-}
-
-// Workgroup barrier that orders LDS traffic only: unlike __syncthreads() it does not wait for
-// outstanding global loads (vmcnt), so the next row's prefetch stays in flight across it.
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-// inclusive prefix sum over lanes (rare tie path; shuffles are fine)
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        uint32_t o = __shfl_up(v, off, kWave);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------
 // chunk access: 8 consecutive columns per lane
@@ -197,26 +153,6 @@ template <int MK> __device__ __forceinline__ float sel_score(float w, float s) {
 #define VLMC_STAMP(i) do {} while (0)
 #endif
 
-// inclusive prefix sum across the 64 lanes with DPP row shifts + row broadcasts
-__device__ __forceinline__ uint32_t wave_incl_scan_u32_dpp(uint32_t v) {
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x111, 0xF, 0xF, false));   // row_shr:1
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x112, 0xF, 0xF, false));   // row_shr:2
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x114, 0xF, 0xF, false));   // row_shr:4
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x118, 0xF, 0xF, false));   // row_shr:8
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x142, 0xA, 0xF, false));   // row_bcast:15 -> rows 1,3
-    v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x143, 0xC, 0xF, false));   // row_bcast:31 -> rows 2,3
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32_dpp(uint32_t v) {
-    v = max(v, uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0xB1, 0xF, 0xF, true)));
-    v = max(v, uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x4E, 0xF, 0xF, true)));
-    v = max(v, uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x141, 0xF, 0xF, true)));
-    v = max(v, uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x140, 0xF, 0xF, true)));
-    return max(max(uint32_t(__builtin_amdgcn_readlane(int(v), 0)), uint32_t(__builtin_amdgcn_readlane(int(v), 16))),
-               max(uint32_t(__builtin_amdgcn_readlane(int(v), 32)), uint32_t(__builtin_amdgcn_readlane(int(v), 48))));
-}
-__device__ __forceinline__ uint32_t wave_min_u32_dpp(uint32_t v) { return ~wave_max_u32_dpp(~v); }
-
 constexpr int kBins = 64;
 constexpr int kSample = 32;
 
@@ -228,16 +164,6 @@ template <int NW> struct RowSmem {
     float fsum[NW];
     uint32_t cut_col;
 };
-
-// workgroup-wide sync of LDS traffic; a single-wave workgroup only needs program order
-template <int NW> __device__ __forceinline__ void row_sync() {
-    if constexpr (NW > 1) {
-        lds_barrier();
-    } else {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-}
 
 // One row by the NW waves whose lanes are numbered `tid` = 0 .. 64*NW-1 and who own `sm`.
 template <typename T, int CH, int NW, bool ALIGNED, int MK = kMetricWanda>
@@ -476,7 +402,7 @@ __device__ __forceinline__ void select_row_body(const SelBatch &b, const SelJob 
     VLMC_STAMP(5);
 #ifndef VLMC_STAMPS
     if (row_sums) {
-        const float tot = wave_sum_f32_dpp(fsum);
+        const float tot = wave_sum_f32_dpp_pairwise(fsum);
         if constexpr (NW > 1) {
             if (lane == 0) sm.fsum[wave] = tot;
             lds_barrier();
@@ -559,10 +485,6 @@ constexpr int kCand = kMatBins + 32;
 constexpr int kWsWords = kCand + 2 * kCandCap;
 enum { C_LO = 0, C_SHIFT, C_BELOW, C_NANC, C_LOB, C_RANKB, C_NONE, C_FAIL, C_DONE, C_NCAND, C_BAR_A, C_BAR_B, C_BAR_A1, C_BAR_A2 };
 
-__device__ __forceinline__ uint32_t ld_dev(const uint32_t *p) {       // device-scope load (bypasses the CU's L1)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Rank search over a histogram held 4 bins per thread by a 1024-thread workgroup (bins past the histogram's
 // end are passed as 0): finds the bin with cum <= need < cum + h.  Returns false if need >= total.
 __device__ bool block_find_rank(const uint32_t (&h)[4], uint32_t need, uint32_t *red /*>= 20 u32 of LDS*/, uint32_t &bin,
@@ -578,11 +500,7 @@ __device__ bool block_find_rank(const uint32_t (&h)[4], uint32_t need, uint32_t 
     const uint32_t hi = off + incl, lo = hi - s;
     if (lo <= need && need < hi) {
         uint32_t cum = lo;
-        int i = 0;
-        for (; i < 3; ++i) {
-            if (cum + h[i] > need) break;
-            cum += h[i];
-        }
+        const int i = walk_bins(h, need, cum);
         red[16] = uint32_t(tid * 4 + i);
         red[17] = cum;
         red[18] = h[i];                                          // population of that bin (read by callers that need it)
@@ -612,11 +530,7 @@ __device__ void block_find_rank2(const uint32_t (&h)[4], uint32_t need_a, uint32
         const uint32_t need = which ? need_b : need_a;
         if (lo <= need && need < hi) {
             uint32_t cum = lo;
-            int i = 0;
-            for (; i < 3; ++i) {
-                if (cum + h[i] > need) break;
-                cum += h[i];
-            }
+            const int i = walk_bins(h, need, cum);
             red[which ? 20 : 16] = uint32_t(tid * 4 + i);
         }
     }
@@ -625,11 +539,6 @@ __device__ void block_find_rank2(const uint32_t (&h)[4], uint32_t need_a, uint32
     bin_b = red[20];
     __syncthreads();
 }
-
-// Key used inside the streaming passes: score >= +0 or NaN, so clearing the sign bit orders every finite score
-// and +inf like score_key() and leaves NaNs above +inf (0x7F800001..0x7FFFFFFF) -- one instruction.  A bin that
-// reaches above +inf is handed to the fallback, which uses score_key()'s single NaN key.
-__device__ __forceinline__ uint32_t stream_key(float sc) { return __float_as_uint(sc) & 0x7FFFFFFFu; }
 
 template <typename T>
 __device__ __forceinline__ uint32_t element_key(const SelJob &jb, uint32_t e) {
@@ -1045,17 +954,13 @@ __global__ __launch_bounds__(1024) void matrix_resolve_kernel(const SelBatch b) 
 //       hundred per linear) to the candidate list                                    -- barrier B
 //   P3  every workgroup radix-selects the exact threshold among the candidates in LDS
 //   P4  apply from the registers: one compare per key -> mask bytes + zeroed weights.
-// Barriers: one arrival counter per barrier in the control block, device-scope atomics only (no L2
-// write-back fences, see matrix_count_kernel).  The grid never exceeds one workgroup per CU, so all
-// workgroups are resident on an otherwise idle GPU; if they are not (CUs held by another stream), the
-// bounded spin runs out and a waiter raises the barrier's fail bit: then NO workgroup of the job passes that
-// barrier, nobody touches W or the mask, and the job's last workgroup to finish (done counter) does the exact
+// Barriers: grid_arrive_wait (grid_sync.hpp) on one arrival counter per barrier in the control block (ws + kCtrl + C_BAR_*;
+// no L2 write-back fences, see matrix_count_kernel).  When a barrier fails, NO workgroup of the job passes it, nobody
+// touches W or the mask, and the job's last workgroup to finish (done counter) does the exact
 // streaming select over the whole matrix (matrix_resolve_job<WRITE_ALL>) -- as it does when the sampled bracket
-// missed rank k, the bin reaches the NaN keys or a skewed bin overflows one workgroup's slot.  Every wave therefore
-// reaches the end of the kernel whatever the residency.
+// missed rank k, the bin reaches the NaN keys or a skewed bin overflows one workgroup's slot.
 // The job's global histogram and control words must be ZERO on entry; the last workgroup zeroes them again.
 // ------------------------------------------------------------------------------------------
-constexpr uint32_t kBarFail = 0x80000000u;
 constexpr int kFusedCand = 4096;                 // candidate keys a workgroup can hold (more => exact fallback)
 constexpr int kSlotArea = 12288;                 // words of the workspace's candidate area used for the slots
 constexpr int kSlotMax = 128;                    // candidate keys one workgroup may publish: min(128, kSlotArea / workgroups)
@@ -1063,27 +968,6 @@ constexpr int kMaxFusedWgs = 256;                // => at least 48 keys per slot
 constexpr int kHist1 = kCand + kSlotArea;        // global histograms of the refinement levels 1 and 2 (2 x 2048 words)
 constexpr uint32_t kSlotEmpty = 0xFFFFFFFFu, kSlotOverflow = 0xFFFFFFFEu;   // (keys are relative to the bin: < 2^22)
 constexpr int kFusedMaxIn = 8192;                // in_features the LDS copy of sqrt(scaler_row) can hold
-constexpr uint32_t kSpinMax = 1u << 12;          // x (device-scope load + s_sleep, ~2.2 us) ~ 9 ms; a barrier normally takes < 20 us
-
-// tid 0 of a workgroup: arrive at the barrier word and wait for `n` arrivals.  false = the barrier failed.
-// The fail bit can only be set (compare-and-swap) while the count is still short, and whoever arrives or polls
-// afterwards sees it before the count: either every workgroup of the job passes the barrier or none does.
-__device__ __forceinline__ bool grid_arrive_wait(uint32_t *ws, int which, uint32_t n) {
-    uint32_t *ctr = ws + kCtrl + which;
-    uint32_t v = atomicAdd(ctr, 1u) + 1u;
-    for (uint32_t it = 0;; ++it) {
-        if (v & kBarFail) return false;
-        if (v >= n) return true;
-        if (it >= kSpinMax) {                                    // give up: declare the failure unless it completed meanwhile
-            const uint32_t seen = atomicCAS(ctr, v, v | kBarFail);
-            if (seen == v) return false;
-            v = seen;
-            continue;
-        }
-        __builtin_amdgcn_s_sleep(8);
-        v = ld_dev(ctr);
-    }
-}
 
 #ifdef VLMC_FUSED_STAMPS
 // diagnostic build only (never shipped): 100 MHz wall-clock stamps of workgroup 0 / the last workgroup of each job
@@ -1200,7 +1084,7 @@ __global__ __launch_bounds__(1024, 1) void matrix_fused_kernel(const SelBatch b)
 #ifndef VLMC_FUSED_STAMP_SCAN
         VLMC_FSTAMP(2);
 #endif
-        if (tid == 0) red[34] = grid_arrive_wait(ws, C_BAR_A, jb.nwg) ? 1u : 0u;      // ---- barrier A
+        if (tid == 0) red[34] = grid_arrive_wait(ws + kCtrl + C_BAR_A, jb.nwg) ? 1u : 0u;      // ---- barrier A
         __syncthreads();
         fail = red[34] == 0;
         VLMC_FSTAMP(3);
@@ -1265,7 +1149,7 @@ __global__ __launch_bounds__(1024, 1) void matrix_fused_kernel(const SelBatch b)
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
-                if (tid == 0) red[34] = grid_arrive_wait(ws, level == 1 ? C_BAR_A1 : C_BAR_A2, jb.nwg) ? 1u : 0u;
+                if (tid == 0) red[34] = grid_arrive_wait(ws + kCtrl + (level == 1 ? C_BAR_A1 : C_BAR_A2), jb.nwg) ? 1u : 0u;
                 __syncthreads();
                 fail = red[34] == 0;
                 if (!fail) {
@@ -1384,7 +1268,7 @@ __global__ __launch_bounds__(1024, 1) void matrix_fused_kernel(const SelBatch b)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 VLMC_FSTAMP(4);
-                if (tid == 0) red[34] = grid_arrive_wait(ws, C_BAR_B, jb.nwg) ? 1u : 0u;     // ---- barrier B
+                if (tid == 0) red[34] = grid_arrive_wait(ws + kCtrl + C_BAR_B, jb.nwg) ? 1u : 0u;     // ---- barrier B
                 __syncthreads();
                 fail = red[34] == 0 || b.p0 == 2;                // (test hook 2: fail with the decided chunks already written)
                 VLMC_FSTAMP(5);
