@@ -1,5 +1,5 @@
-"""The compiled host path (csrc/fastpath/fast_bind.cpp -> vlmc/_fast) and the ctypes route call the same C ABI: same bits, same
-refusals."""
+"""The compiled host path (csrc/fastpath/fast_bind.cpp -> vlmc/_fast) and the ctypes back end (vlmc/ops.py: _ctypes_route) call the same
+C ABI under one contract: same bits, same refusals."""
 import pytest
 import torch
 
@@ -42,7 +42,7 @@ def test_linear_routes_agree(dtype, monkeypatch):
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16, torch.float32])
 def test_row_mapped_linear_routes_agree(dtype, monkeypatch):
     """vlmc_linear_fwd_rows through vlmc/_fast and through ctypes: same outputs (16-bit group launch; fp32 one launch per member), and
-    the calls the kernel does not take fall through to the ctypes route's checks."""
+    a call the kernel does not take raises what the public op says."""
     from vlmc import ops
     g = torch.Generator(device=DEV).manual_seed(3)
     lengths, tp, K = [9, 3, 12, 1, 7], 12, 256
@@ -55,7 +55,7 @@ def test_row_mapped_linear_routes_agree(dtype, monkeypatch):
     a, c = _both(monkeypatch, lambda: ops.linear_fwd_rows(x, ws, bs, rowmap, len(real)))
     assert len(a) == 2 and all(p.shape == (len(lengths), tp, w.shape[0]) and torch.equal(p, q) for p, q, w in zip(a, c, ws))
     with pytest.raises(ValueError):
-        ops.linear_fwd_rows(x, ws, bs, rowmap[:-1].contiguous(), len(real))          # (the compiled path answers None, the ctypes route says why)
+        ops.linear_fwd_rows(x, ws, bs, rowmap[:-1].contiguous(), len(real))          # (the back end answers None, the public op says why)
 
 
 def test_attention_products_routes_agree(monkeypatch):
@@ -130,3 +130,113 @@ def test_sdpa_and_rms_norm_routes_agree(monkeypatch):
         with pytest.raises(TypeError):
             ops.rms_norm(x, w.float(), 1e-6, 0)
         monkeypatch.undo()
+
+
+def _each_route(monkeypatch):
+    """The compiled route, then the ctypes one (`ops._fast` is looked up per call)."""
+    from vlmc import ops
+    assert ops._fast is not None, "vlmc/_fast is not built (python -c 'import __graft_entry__ as g; g.build()')"
+    yield "compiled"
+    monkeypatch.setattr(ops, "_fast", None)
+    yield "ctypes"
+    monkeypatch.undo()
+
+
+def test_fp32_launches_routes_agree(monkeypatch):
+    """The fp32 kernels behind linear_fwd and attn_matmul through both routes: the loose rows view (`ld = K` for a single row) and the
+    one attn_matmul launch of the ctypes back end."""
+    from vlmc import ops
+    g = torch.Generator(device=DEV).manual_seed(5)
+    x = torch.randn(4, 64, generator=g, device=DEV)
+    w = torch.randn(8, 64, generator=g, device=DEV)
+    b = torch.randn(8, generator=g, device=DEV)
+    for bias in (None, b):
+        a, c = _both(monkeypatch, lambda: ops.linear_fwd(x, w, bias))
+        assert a.dtype == torch.float32 and a.shape == (4, 8) and torch.equal(a, c)
+    wide = torch.randn(1, 200, generator=g, device=DEV)
+    row = wide[:, 70:134]                                                # M = 1, a column slice: stride(0) = 200, the kernel is told ld = K
+    a, c = _both(monkeypatch, lambda: ops.linear_fwd(row, w, b))
+    assert a.shape == (1, 8) and torch.equal(a, c) and torch.equal(a, ops.linear_fwd(row.contiguous(), w, b))
+    p = torch.randn(2, 3, 9, 16, generator=g, device=DEV)
+    q = torch.randn(2, 3, 16, 9, generator=g, device=DEV)
+    a, c = _both(monkeypatch, lambda: ops.attn_matmul(p, q))
+    assert a.dtype == torch.float32 and a.shape == (2, 3, 9, 9) and torch.equal(a, c)
+    a, c = _both(monkeypatch, lambda: ops.attn_matmul(p[1], q[1]))       # 3-D
+    assert a.shape == (3, 9, 9) and torch.equal(a, c) and torch.equal(a, ops.attn_matmul(p, q)[1])
+
+
+def test_row_mean_routes_agree(monkeypatch):
+    from vlmc import ops
+    x = torch.randn(5, 7, 300, generator=torch.Generator(device=DEV).manual_seed(6), device=DEV)
+    for keepdim in (False, True):
+        a, c = _both(monkeypatch, lambda: ops.row_mean(x, keepdim))
+        assert a.shape == ((5, 7, 1) if keepdim else (5, 7)) and torch.equal(a, c)
+        a, c = _both(monkeypatch, lambda: ops.row_mean(x[:, :, :257], keepdim))          # rows 300 apart, read in place
+        assert torch.equal(a, c) and torch.equal(a, ops.row_mean(x[:, :, :257].contiguous(), keepdim))
+        a, c = _both(monkeypatch, lambda: ops.row_mean(x[2, 3:4, :257], keepdim))        # a single row
+        assert a.shape == ((1, 1) if keepdim else (1,)) and torch.equal(a, c)
+        assert torch.equal(a.reshape(-1), ops.row_mean(x[:, :, :257])[2, 3:4])
+
+
+def test_row_mapped_linear_refusals_on_both_routes(monkeypatch):
+    from vlmc import ops
+    x = torch.randn(2, 6, 64, device=DEV).half()
+    w = torch.randn(8, 64, device=DEV).half()
+    rowmap = torch.arange(12, dtype=torch.int32, device=DEV)
+    for route in _each_route(monkeypatch):
+        with pytest.raises(ValueError):
+            ops.linear_fwd_rows(x, [w], [None], rowmap[:-1].contiguous(), 5)             # a short row map
+        with pytest.raises(ValueError):
+            ops.linear_fwd_rows(x, [w] * 5, None, rowmap, 5)                             # more than 4 members
+        with pytest.raises(TypeError):
+            ops.linear_fwd_rows(x, [w, w.float()], None, rowmap, 5)                      # mixed dtypes
+        with pytest.raises(RuntimeError):
+            ops.linear_fwd_rows(x.cpu(), [w], [None], rowmap, 5)                         # no CPU fallback
+        with pytest.raises(RuntimeError):
+            ops.linear_fwd_rows(x, [w], [None], rowmap.cpu(), 5)
+
+
+def test_every_op_refuses_alike_on_both_routes(monkeypatch):
+    """One refused call or more for each of the seven ops: the same exception class on both routes, None under `_try`.  Every one is
+    refused by the host checks, before any launch."""
+    from vlmc import ops
+    x = torch.randn(4, 64, device=DEV)
+    w = torch.randn(8, 64, device=DEV)
+    xh, wh = x.half(), w.half()
+    rowmap = torch.arange(4, dtype=torch.int32, device=DEV)
+    q = torch.randn(1, 2, 5, 16, device=DEV).half()
+    refused = [                      # (op, arguments, keyword arguments, exception class)
+        ("linear_fwd", (xh, w), {}, TypeError),                                          # mixed dtypes
+        ("linear_fwd", (xh[:, :60], wh[:, :60]), {}, TypeError),                         # in_features % 8
+        ("linear_fwd", (x, w, torch.zeros(8, device=DEV).half()), {}, TypeError),        # fp32 with a 16-bit bias
+        ("linear_fwd", (xh.cpu(), wh.cpu()), {}, RuntimeError),
+        ("linear_fwd_group", (xh, [wh, w]), {}, TypeError),
+        ("linear_fwd_group", (x, [w]), {}, TypeError),                                   # fp32: not a group launch
+        ("linear_fwd_group", (xh, []), {}, ValueError),
+        ("linear_fwd_group", (xh, [wh] * 2, [None]), {}, ValueError),                    # fewer biases than weights
+        ("linear_fwd_group", (xh.cpu(), [wh.cpu()] * 5), {}, RuntimeError),
+        ("linear_fwd_rows", (xh, [wh], [None], rowmap, 0), {}, ValueError),              # n_real < 1
+        ("linear_fwd_rows", (xh, [wh], [None], rowmap.long(), 4), {}, ValueError),
+        ("linear_fwd_rows", (x, [w, wh], None, rowmap, 4), {}, TypeError),
+        ("attn_matmul", (xh, wh.t()), {}, TypeError),                                    # 2-D
+        ("attn_matmul", (xh[None], w.t()[None]), {}, TypeError),                         # mixed dtypes
+        ("attn_matmul", (xh[None].cpu(), wh.t()[None].cpu()), {}, RuntimeError),
+        ("rms_norm", (xh, torch.ones(64, device=DEV), 1e-6), {}, TypeError),             # an fp32 weight
+        ("rms_norm", (x, torch.ones(64, device=DEV), 1e-6), {}, TypeError),              # fp32 x
+        ("rms_norm", (xh, torch.ones(64).half(), 1e-6), {}, RuntimeError),               # a CPU weight
+        ("sdpa", (q.float(), q.float(), q.float()), {}, TypeError),
+        ("sdpa", (q, q, q), {"scale": 0.0}, TypeError),
+        ("sdpa", (q, q[:, :, :, :8], q), {}, TypeError),                                 # head_dim of k
+        ("sdpa", (q.cpu(), q.cpu(), q.cpu()), {}, RuntimeError),
+        ("row_mean", (xh,), {}, TypeError),
+        ("row_mean", (x[:, :0],), {}, TypeError),                                        # empty rows
+        ("row_mean", (x.cpu(),), {}, RuntimeError),
+    ]
+    assert {op for op, *_ in refused} == set(ops._FAST_ENTRY_POINTS)
+    for route in _each_route(monkeypatch):
+        for op, args, kw, exc in refused:
+            with pytest.raises(exc) as info:
+                getattr(ops, op)(*args, **kw)
+            assert type(info.value) is exc and (exc is RuntimeError or f"vlmc.{op}: " in str(info.value)), (route, op, info.value)
+            if op in ("linear_fwd", "attn_matmul", "sdpa"):
+                assert getattr(ops, op)(*args, _try=True, **kw) is None, (route, op)

@@ -6,8 +6,10 @@
 // GPUs: the kernels take 10-50 us and the ctypes route (vlmc/ops.py: argument checks, reshape, torch.empty, a job table,
 // 12-20 converted arguments) 8-22 us of host time each -- the host sets the pace.  This module does the same checks, views and
 // allocations through ATen and calls the SAME C ABI (it links libvlmc_hip.so; no kernel lives here): ~2 us per call.
-// vlmc/ops.py uses it when it has been built (__graft_entry__.build() builds it) and falls back to ctypes otherwise -- the
-// results are the library's either way.  PyTorch here is plumbing: tensor metadata, allocation, the autograd / autocast flags.
+// vlmc/ops.py uses it when it has been built (__graft_entry__.build() builds it) and its ctypes back end otherwise -- the
+// results are the library's either way.  One contract for both: op(tensors..., stream) returns the result, or None when the call
+// is not one the kernel takes (vlmc/ops.py then says what was wrong); only a failed launch throws.
+// PyTorch here is plumbing: tensor metadata, allocation, the autograd / autocast flags.
 #include <torch/extension.h>
 
 #include <cstdint>
@@ -43,10 +45,21 @@ bool linear_ok(const at::Tensor &x, const at::Tensor &w, const c10::optional<at:
     return true;
 }
 
-// x as [M, K] rows the kernel can read: K-contiguous, 16-byte aligned rows
-at::Tensor rows_of(const at::Tensor &x, int64_t K) {
-    at::Tensor x2 = x.reshape({-1, K});
-    if (x2.stride(1) != 1 || x2.stride(0) % 8 != 0 || x2.stride(0) < K || !aligned16(x2.data_ptr())) x2 = x2.contiguous();
+// what vlmc/ops.py: linear_f32_supported asks of them (the reference's Q-Former: the fp32 matrix-core kernel behind the same entry points)
+bool linear_ok_f32(const at::Tensor &x, const at::Tensor &w, const c10::optional<at::Tensor> &b) {
+    if (!x.is_cuda() || !w.is_cuda() || x.scalar_type() != at::kFloat || w.scalar_type() != at::kFloat || w.dim() != 2 || x.dim() < 1 ||
+        x.size(-1) != w.size(1) || w.size(1) == 0 || w.stride(1) != 1)
+        return false;
+    return !(b.has_value() && b->defined()) || (b->is_cuda() && b->scalar_type() == at::kFloat && b->is_contiguous());
+}
+
+// x as [M, n] rows the kernel can read in place, copied when it cannot (vlmc/ops.py: _rows).  `aligned` (the 16-bit GEMMs): n-contiguous
+// rows, 16-byte aligned, a multiple of 8 elements apart.  Loose (fp32 and the row kernels): rows that do not overlap; ld = n for a single row
+at::Tensor rows_of(const at::Tensor &x, int64_t n, bool aligned, int64_t &ld) {
+    at::Tensor x2 = x.reshape({-1, n});
+    const int64_t s0 = x2.stride(0);
+    if (x2.stride(1) != 1 || (aligned ? (s0 % 8 != 0 || s0 < n || !aligned16(x2.data_ptr())) : (x2.size(0) > 1 && s0 < n))) x2 = x2.contiguous();
+    ld = (aligned || x2.size(0) > 1) ? x2.stride(0) : n;
     return x2;
 }
 
@@ -56,32 +69,39 @@ std::vector<int64_t> lead_shape(const at::Tensor &x, int64_t N) {
     return s;
 }
 
-// fp32 (the reference's Q-Former: vlmc/ops.py: linear_f32_supported): the fp32 matrix-core kernel behind the same entry point
-py::object linear_fwd_f32(const at::Tensor &x, const at::Tensor &w, const c10::optional<at::Tensor> &b, int64_t stream) {
-    if (!x.is_cuda() || !w.is_cuda() || x.scalar_type() != at::kFloat || w.dim() != 2 || x.dim() < 1 || x.size(-1) != w.size(1) || w.size(1) == 0 ||
-        w.stride(1) != 1)
-        return py::none();
-    const bool has_b = b.has_value() && b->defined();
-    if (has_b && (!b->is_cuda() || b->scalar_type() != at::kFloat || !b->is_contiguous())) return py::none();
-    const int64_t N = w.size(0), K = w.size(1);
-    at::Tensor x2 = x.reshape({-1, K});
-    if (x2.stride(1) != 1 || (x2.size(0) > 1 && x2.stride(0) < K)) x2 = x2.contiguous();
-    const int64_t M = x2.size(0);
-    at::Tensor y = at::empty({M, N}, x.options());
-    check(vlmc_linear_fwd(x2.data_ptr(), w.data_ptr(), has_b ? b->data_ptr() : nullptr, VLMC_F32, M, N, K, M > 1 ? x2.stride(0) : K, w.stride(0),
-                          y.data_ptr(), N, reinterpret_cast<void *>(stream)));
-    return py::cast(y.reshape(lead_shape(x, N)));
+// the table of a group launch and its fresh outputs [M, N]
+void fill_jobs(vlmc_linear_job *jobs, std::vector<at::Tensor> &ys, const at::Tensor &x, int64_t M, const std::vector<at::Tensor> &ws,
+               const std::vector<c10::optional<at::Tensor>> &bs) {
+    ys.reserve(ws.size());
+    for (size_t g = 0; g < ws.size(); ++g) {
+        const int64_t N = ws[g].size(0);
+        ys.push_back(at::empty({M, N}, x.options()));
+        jobs[g].W = ws[g].data_ptr();
+        jobs[g].bias = (bs[g].has_value() && bs[g]->defined()) ? bs[g]->data_ptr() : nullptr;
+        jobs[g].Y = ys.back().data_ptr();
+        jobs[g].N = N;
+        jobs[g].ldw = ws[g].stride(0);
+        jobs[g].ldy = N;
+    }
 }
 
+py::object group_outputs(const at::Tensor &x, const std::vector<at::Tensor> &ys) {
+    py::list out;
+    for (const at::Tensor &y : ys) out.append(py::cast(y.reshape(lead_shape(x, y.size(1)))));
+    return std::move(out);
+}
+
+// y = x @ weight.T + bias; 16-bit, or fp32 on the fp32 kernel
 py::object linear_fwd(const at::Tensor &x, const at::Tensor &w, const c10::optional<at::Tensor> &b, int64_t stream) {
-    if (w.scalar_type() == at::kFloat) return linear_fwd_f32(x, w, b, stream);
-    if (!linear_ok(x, w, b)) return py::none();
+    const bool f32 = w.scalar_type() == at::kFloat;
+    if (!(f32 ? linear_ok_f32(x, w, b) : linear_ok(x, w, b))) return py::none();
     const int64_t N = w.size(0), K = w.size(1);
-    const at::Tensor x2 = rows_of(x, K);
+    int64_t ld;
+    const at::Tensor x2 = rows_of(x, K, !f32, ld);
     const int64_t M = x2.size(0);
     at::Tensor y = at::empty({M, N}, x.options());
     const void *bias = (b.has_value() && b->defined()) ? b->data_ptr() : nullptr;
-    check(vlmc_linear_fwd(x2.data_ptr(), w.data_ptr(), bias, dtype_code(x.scalar_type()), M, N, K, x2.stride(0), w.stride(0), y.data_ptr(), N,
+    check(vlmc_linear_fwd(x2.data_ptr(), w.data_ptr(), bias, f32 ? VLMC_F32 : dtype_code(x.scalar_type()), M, N, K, ld, w.stride(0), y.data_ptr(), N,
                           reinterpret_cast<void *>(stream)));
     return py::cast(y.reshape(lead_shape(x, N)));
 }
@@ -93,69 +113,37 @@ py::object linear_fwd_group(const at::Tensor &x, const std::vector<at::Tensor> &
     for (size_t g = 0; g < n; ++g)
         if (!linear_ok(x, ws[g], bs[g]) || ws[g].size(1) != ws[0].size(1)) return py::none();
     const int64_t K = ws[0].size(1);
-    const at::Tensor x2 = rows_of(x, K);
+    int64_t ld;
+    const at::Tensor x2 = rows_of(x, K, true, ld);
     const int64_t M = x2.size(0);
     vlmc_linear_job jobs[4];
     std::vector<at::Tensor> ys;
-    ys.reserve(n);
-    for (size_t g = 0; g < n; ++g) {
-        const int64_t N = ws[g].size(0);
-        ys.push_back(at::empty({M, N}, x.options()));
-        jobs[g].W = ws[g].data_ptr();
-        jobs[g].bias = (bs[g].has_value() && bs[g]->defined()) ? bs[g]->data_ptr() : nullptr;
-        jobs[g].Y = ys.back().data_ptr();
-        jobs[g].N = N;
-        jobs[g].ldw = ws[g].stride(0);
-        jobs[g].ldy = N;
-    }
-    check(vlmc_linear_fwd_group(x2.data_ptr(), jobs, int(n), dtype_code(x.scalar_type()), M, K, x2.stride(0), reinterpret_cast<void *>(stream)));
-    py::list out;
-    for (size_t g = 0; g < n; ++g) out.append(py::cast(ys[g].reshape(lead_shape(x, ws[g].size(0)))));
-    return std::move(out);
+    fill_jobs(jobs, ys, x, M, ws, bs);
+    check(vlmc_linear_fwd_group(x2.data_ptr(), jobs, int(n), dtype_code(x.scalar_type()), M, K, ld, reinterpret_cast<void *>(stream)));
+    return group_outputs(x, ys);
 }
 
-// the same over a ROW MAP (a padded group of ragged calibration samples; vlmc/ops.py: linear_fwd_rows): 16-bit or fp32; None when the
-// call is not one the kernel takes (the caller's ctypes route then raises with the reason)
+// the same over a ROW MAP (a padded group of ragged calibration samples; vlmc/ops.py: linear_fwd_rows): 16-bit or fp32
 py::object linear_fwd_rows(const at::Tensor &x, const std::vector<at::Tensor> &ws, const std::vector<c10::optional<at::Tensor>> &bs,
                            const at::Tensor &rowmap, int64_t n_real, int64_t stream) {
     const size_t n = ws.size();
-    if (n < 1 || n > 4 || bs.size() != n || !x.is_cuda()) return py::none();
+    if (n < 1 || n > 4 || bs.size() != n) return py::none();
     const bool f32 = x.scalar_type() == at::kFloat;
-    for (size_t g = 0; g < n; ++g) {
-        if (ws[g].dim() != 2 || ws[g].size(1) != ws[0].size(1)) return py::none();
-        if (f32) {
-            const at::Tensor &w = ws[g];
-            if (!w.is_cuda() || w.scalar_type() != at::kFloat || x.dim() < 1 || x.size(-1) != w.size(1) || w.size(1) == 0 || w.stride(1) != 1) return py::none();
-            if (bs[g].has_value() && bs[g]->defined() && (!bs[g]->is_cuda() || bs[g]->scalar_type() != at::kFloat || !bs[g]->is_contiguous())) return py::none();
-        } else if (!linear_ok(x, ws[g], bs[g])) {
-            return py::none();
-        }
-    }
+    for (size_t g = 0; g < n; ++g)
+        if (!(f32 ? linear_ok_f32(x, ws[g], bs[g]) : linear_ok(x, ws[g], bs[g]))) return py::none();
     const int64_t K = ws[0].size(1);
-    at::Tensor x2 = x.reshape({-1, K});
-    if (x2.stride(1) != 1 || x2.stride(0) < K || (!f32 && (x2.stride(0) % 8 != 0 || !aligned16(x2.data_ptr())))) x2 = x2.contiguous();
+    int64_t ld;
+    const at::Tensor x2 = rows_of(x, K, !f32, ld);
     const int64_t M = x2.size(0);
     if (!rowmap.is_cuda() || rowmap.scalar_type() != at::kInt || rowmap.dim() != 1 || rowmap.size(0) != M || !rowmap.is_contiguous() || n_real < 1 ||
         n_real > M)
         return py::none();
     vlmc_linear_job jobs[4];
     std::vector<at::Tensor> ys;
-    ys.reserve(n);
-    for (size_t g = 0; g < n; ++g) {
-        const int64_t N = ws[g].size(0);
-        ys.push_back(at::empty({M, N}, x.options()));
-        jobs[g].W = ws[g].data_ptr();
-        jobs[g].bias = (bs[g].has_value() && bs[g]->defined()) ? bs[g]->data_ptr() : nullptr;
-        jobs[g].Y = ys.back().data_ptr();
-        jobs[g].N = N;
-        jobs[g].ldw = ws[g].stride(0);
-        jobs[g].ldy = N;
-    }
-    check(vlmc_linear_fwd_rows(x2.data_ptr(), jobs, int(n), f32 ? VLMC_F32 : dtype_code(x.scalar_type()), M, K, x2.stride(0),
+    fill_jobs(jobs, ys, x, M, ws, bs);
+    check(vlmc_linear_fwd_rows(x2.data_ptr(), jobs, int(n), f32 ? VLMC_F32 : dtype_code(x.scalar_type()), M, K, ld,
                                static_cast<const int32_t *>(rowmap.data_ptr()), n_real, reinterpret_cast<void *>(stream)));
-    py::list out;
-    for (size_t g = 0; g < n; ++g) out.append(py::cast(ys[g].reshape(lead_shape(x, ws[g].size(0)))));
-    return std::move(out);
+    return group_outputs(x, ys);
 }
 
 // torch.matmul(a, b) for the batched products of attention; None when vlmc_attn_matmul does not compute the call
@@ -206,13 +194,12 @@ py::object attn_matmul(const at::Tensor &a, const at::Tensor &b, int64_t stream)
 py::object row_mean(const at::Tensor &x, bool keepdim, int64_t stream) {
     if (!x.is_cuda() || x.scalar_type() != at::kFloat || x.dim() < 1 || x.size(-1) == 0) return py::none();
     const int64_t n = x.size(-1);
-    at::Tensor x2 = x.reshape({-1, n});
-    if (x2.stride(1) != 1 || (x2.size(0) > 1 && x2.stride(0) < n)) x2 = x2.contiguous();
-    const int64_t rows = x2.size(0);
+    int64_t ld;
+    const at::Tensor x2 = rows_of(x, n, false, ld);
     std::vector<int64_t> oshape(x.sizes().begin(), x.sizes().end() - 1);
     if (keepdim) oshape.push_back(1);
     at::Tensor out = at::empty(oshape, x.options());
-    check(vlmc_row_mean(static_cast<const float *>(x2.data_ptr()), rows, n, rows > 1 ? x2.stride(0) : n, static_cast<float *>(out.data_ptr()),
+    check(vlmc_row_mean(static_cast<const float *>(x2.data_ptr()), x2.size(0), n, ld, static_cast<float *>(out.data_ptr()),
                         reinterpret_cast<void *>(stream)));
     return py::cast(out);
 }
@@ -241,11 +228,11 @@ py::object rms_norm(const at::Tensor &x, const at::Tensor &w, double eps, int64_
         x.size(-1) != w.size(0) || w.size(0) == 0 || !w.is_contiguous())
         return py::none();
     const int64_t n = w.size(0);
-    at::Tensor x2 = x.reshape({-1, n});
-    if (x2.stride(1) != 1 || (x2.size(0) > 1 && x2.stride(0) < n)) x2 = x2.contiguous();
+    int64_t ld;
+    const at::Tensor x2 = rows_of(x, n, false, ld);
     const int64_t rows = x2.size(0);
     at::Tensor out = at::empty({rows, n}, x.options());
-    check(vlmc_rms_norm(x2.data_ptr(), dtype_code(x.scalar_type()), rows, n, rows > 1 ? x2.stride(0) : n, w.data_ptr(), float(eps), int(rsqrt_mode),
+    check(vlmc_rms_norm(x2.data_ptr(), dtype_code(x.scalar_type()), rows, n, ld, w.data_ptr(), float(eps), int(rsqrt_mode),
                         out.data_ptr(), n, reinterpret_cast<void *>(stream)));
     return py::cast(out.reshape(x.sizes()));
 }
@@ -253,13 +240,15 @@ py::object rms_norm(const at::Tensor &x, const at::Tensor &w, double eps, int64_
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-    m.doc() = "compiled host path of vlmc_linear_fwd / vlmc_linear_fwd_group / vlmc_attn_matmul (same C ABI as the ctypes route)";
+    m.doc() = "compiled host path of vlmc_linear_fwd / vlmc_linear_fwd_group / vlmc_linear_fwd_rows / vlmc_attn_matmul / vlmc_row_mean / "
+              "vlmc_rms_norm / vlmc_sdpa_fwd (same C ABI and same contract as the ctypes back end of vlmc/ops.py: None = not taken)";
     m.def("linear_fwd", &linear_fwd, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("stream"));
     m.def("linear_fwd_group", &linear_fwd_group, py::arg("x"), py::arg("weights"), py::arg("biases"), py::arg("stream"));
     m.def("attn_matmul", &attn_matmul, py::arg("a"), py::arg("b"), py::arg("stream"));
     m.def("row_mean", &row_mean, py::arg("x"), py::arg("keepdim"), py::arg("stream"));
     m.def("sdpa", &sdpa, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"), py::arg("causal"), py::arg("stream"));
     m.def("rms_norm", &rms_norm, py::arg("x"), py::arg("weight"), py::arg("eps"), py::arg("rsqrt_mode"), py::arg("stream"));
-    m.def("linear_fwd_rows", &linear_fwd_rows);
+    m.def("linear_fwd_rows", &linear_fwd_rows, py::arg("x"), py::arg("weights"), py::arg("biases"), py::arg("rowmap"), py::arg("n_real"),
+          py::arg("stream"));
     m.def("abi_version", []() { return vlmc_abi_version(); });
 }

@@ -231,7 +231,7 @@ def linear(x, weight, bias=None):
             p = _prepare(x, weight, bias)                            # what autocast would do to x and the bias
             if p is not None:
                 stats["kernel"] += 1
-                return ops.linear_fwd(p[0], weight, p[1], _checked=True)
+                return ops.linear_fwd(p[0], weight, p[1])
     stats["library"] += 1
     return F.linear(x, weight, bias)
 
@@ -345,7 +345,7 @@ class _Tracker:
                             outs = ops.linear_fwd_rows(xin, [g.weight for g in group], biases, rm[0], rm[1])
                             stats["kernel_rows"] += len(group)
                         else:
-                            outs = ops.linear_fwd_group(xin, [g.weight for g in group], biases, _checked=True)
+                            outs = ops.linear_fwd_group(xin, [g.weight for g in group], biases)
                         stats["kernel"] += len(group)
                         stats["grouped_launches"] += 1
                         for g, y in zip(group[1:], outs[1:]):

@@ -71,13 +71,13 @@ _MODES = {"row": _lib.SEL_ROW, "matrix": _lib.SEL_MATRIX, "nm": _lib.SEL_NM}
 _hessian_ws = Workspace()
 
 
-_FAST_ENTRY_POINTS = ("linear_fwd", "linear_fwd_group", "attn_matmul", "row_mean", "rms_norm", "sdpa")
+_FAST_ENTRY_POINTS = ("linear_fwd", "linear_fwd_group", "linear_fwd_rows", "attn_matmul", "row_mean", "rms_norm", "sdpa")
 
 
 def _load_fast():
-    """The compiled host path (csrc/fastpath/fast_bind.cpp -> vlmc/_fast*.so) for linear_fwd / linear_fwd_group / attn_matmul:
-    the same C ABI, ~2 us of host time per call instead of 8-22 through ctypes.  None when it has not been built, when
-    `VLMC_FAST=0`, or when `VLMC_LIB` points at another build of the library (the module links the in-tree one)."""
+    """The compiled host path (csrc/fastpath/fast_bind.cpp -> vlmc/_fast*.so) of `_FAST_ENTRY_POINTS`: the same C ABI, ~2 us of host
+    time per call instead of 8-22 through ctypes.  None when it has not been built, when `VLMC_FAST=0`, or when `VLMC_LIB` points at
+    another build of the library (the module links the in-tree one)."""
     if not config.flag("VLMC_FAST") or config.text("VLMC_LIB"):
         return None
     try:
@@ -87,7 +87,7 @@ def _load_fast():
     if _fast.abi_version() != _lib.header_abi_version():
         raise ImportError("vlmc/_fast was built against another ABI version of libvlmc_hip.so; rebuild (make -C vlm-compression_amd/csrc/fastpath)")
     _lib.load()
-    missing = [n for n in _FAST_ENTRY_POINTS if not hasattr(_fast, n)]
+    missing = sorted(set(_FAST_ENTRY_POINTS) - set(dir(_fast)))
     if missing:                                                          # a stale build at the same ABI: one route for everything, not a mix
         import warnings
         warnings.warn(f"vlmc/_fast lacks {missing}: rebuild it (make -C vlm-compression_amd/csrc/fastpath); using the ctypes route")
@@ -96,6 +96,20 @@ def _load_fast():
 
 
 _fast = _load_fast()
+_16BIT = (torch.float16, torch.bfloat16)
+LINEAR_GROUP_MAX = 4
+
+
+def _rows(x: torch.Tensor, n: int, aligned: bool = False):
+    """(x2, rows, ld): x [.., n] as [rows, n] rows a kernel reads in place, copied when it cannot -- unit stride along n and rows
+    that do not overlap (stride(0) >= n; a single row has no stride to speak of: ld = n).  `aligned` (the 16-bit GEMMs' 16-byte loads):
+    stride(0) a multiple of 8 elements and a 16-byte-aligned pointer as well, for a single row too.  (The copy is `.contiguous()`:
+    a tensor that is contiguous already comes back as it is, and the entry point refuses it if it is misaligned.)"""
+    x2 = x.reshape(-1, n)
+    rows, ld = x2.shape[0], x2.stride(0)
+    if x2.stride(1) != 1 or (ld % 8 != 0 or ld < n or x2.data_ptr() % 16 != 0 if aligned else rows > 1 and ld < n):
+        x2 = x2.contiguous()                                 # (an expanded input has stride(0) == 0 < n)
+    return x2, rows, x2.stride(0) if aligned or rows > 1 else n
 
 
 def linear_f32_supported(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None) -> bool:
@@ -106,182 +120,12 @@ def linear_f32_supported(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tens
             and (bias is None or (bias.is_cuda and bias.dtype is f32 and bias.is_contiguous())))
 
 
-def _linear_fwd_f32(x, weight, bias):
-    N, K = weight.shape
-    x2 = x.reshape(-1, K)
-    if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < K):
-        x2 = x2.contiguous()
-    M = x2.shape[0]
-    y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().vlmc_linear_fwd(x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None, _lib.F32, M, N, K,
-                                           x2.stride(0) if M > 1 else K, weight.stride(0), y.data_ptr(), N, _stream()))
-    return y.reshape(*x.shape[:-1], N)
-
-
 def linear_fwd_supported(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None) -> bool:
     """Whether `linear_fwd` takes this call on its 16-bit kernels: 16-bit activations and weights of one dtype on the GPU, K a multiple of 8."""
     return (x.is_cuda and weight.is_cuda and x.dtype == weight.dtype and x.dtype in (torch.float16, torch.bfloat16)
             and weight.dim() == 2 and x.shape[-1] == weight.shape[1] and weight.shape[1] % 8 == 0 and weight.stride(1) == 1
             and weight.stride(0) % 8 == 0 and weight.data_ptr() % 16 == 0
             and (bias is None or (bias.is_cuda and bias.dtype == weight.dtype and bias.is_contiguous())))
-
-
-def linear_fwd(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, _checked: bool = False,
-               _try: bool = False) -> torch.Tensor:
-    """y = x @ weight.T + bias on the batch-invariant MFMA kernel (`F.linear` inside the calibration replay's block
-    forwards, wanda_pruner.py:308-311,343-346): a row of y depends on its row of x only, whatever else is in the call.
-    `_try`: return None instead of raising when the call is not one the kernel takes.  fp32 tensors (the reference's Q-Former): the
-    fp32 matrix-core kernel, the same invariance."""
-    if weight.dtype is torch.float32 and x.dtype is torch.float32:
-        y = None
-        if _fast is not None and x.is_cuda:
-            y = _fast.linear_fwd(x, weight, bias, _stream())
-        elif linear_f32_supported(x, weight, bias):
-            y = _linear_fwd_f32(x, weight, bias)
-        if y is None and not _try:
-            _need_gpu(x, weight, bias)
-            raise TypeError("vlmc.linear_fwd: fp32 x [.., K], weight [N, K] with contiguous rows and a contiguous fp32 bias expected")
-        return y
-    if _fast is not None:
-        if not x.is_cuda:
-            _need_gpu(x, weight, bias)
-        y = _fast.linear_fwd(x, weight, bias, _stream())
-        if y is None and not _try:
-            _need_gpu(x, weight, bias)
-            raise TypeError("vlmc.linear_fwd: fp16/bf16 tensors of one dtype with in_features % 8 == 0 expected")
-        return y
-    if _try and not (x.is_cuda and linear_fwd_supported(x, weight, bias)):
-        return None
-    _need_gpu(x, weight, bias)
-    if not _checked and not _try and not linear_fwd_supported(x, weight, bias):
-        raise TypeError("vlmc.linear_fwd: fp16/bf16 tensors of one dtype with in_features % 8 == 0 expected")
-    N, K = weight.shape
-    x2 = x.reshape(-1, K)
-    if x2.stride(1) != 1 or x2.stride(0) % 8 != 0 or x2.stride(0) < K or x2.data_ptr() % 16 != 0:
-        x2 = x2.contiguous()                                 # (an expanded input has stride(0) == 0 < K)
-    M = x2.shape[0]
-    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    _lib.check(_lib.load().vlmc_linear_fwd(x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                           _dtype_code(x), M, N, K, x2.stride(0), weight.stride(0), y.data_ptr(), N, _stream()))
-    return y.reshape(*x.shape[:-1], N)
-
-
-LINEAR_GROUP_MAX = 4
-
-
-_group_jobs = {}           # (W pointer, N, ldw, bias pointer) per member -> the launch's job table, everything but Y filled in
-
-
-def linear_fwd_group(x: torch.Tensor, weights, biases=None, _checked: bool = False) -> list:
-    """[x @ w.T + b for w, b in zip(weights, biases)] in ONE launch of the batch-invariant kernel: up to 4 linears fed the
-    same activations (q / k / v, wi_0 / wi_1, cross-attention k / v).  Every output has the bits `linear_fwd` gives it;
-    the launch shares the chip between the products (include/vlmc.h: vlmc_linear_fwd_group)."""
-    n = len(weights)
-    if biases is None:
-        biases = [None] * n
-    if _fast is not None:
-        if not x.is_cuda:
-            _need_gpu(x, *weights)
-        outs = _fast.linear_fwd_group(x, list(weights), list(biases), _stream())
-        if outs is None:
-            if not 1 <= n <= LINEAR_GROUP_MAX or len(biases) != n:
-                raise ValueError(f"linear_fwd_group takes 1..{LINEAR_GROUP_MAX} weights and as many biases")
-            _need_gpu(x, *weights, *[b for b in biases if b is not None])
-            raise TypeError("vlmc.linear_fwd_group: fp16/bf16 tensors of one dtype with in_features % 8 == 0 expected")
-        return outs
-    if not _checked:
-        if not 1 <= n <= LINEAR_GROUP_MAX or len(biases) != n:
-            raise ValueError(f"linear_fwd_group takes 1..{LINEAR_GROUP_MAX} weights and as many biases")
-        _need_gpu(x, *weights, *[b for b in biases if b is not None])
-        for w, b in zip(weights, biases):
-            if not linear_fwd_supported(x, w, b):
-                raise TypeError("vlmc.linear_fwd_group: fp16/bf16 tensors of one dtype with in_features % 8 == 0 expected")
-    K = weights[0].shape[1]
-    x2 = x.reshape(-1, K)
-    if x2.stride(1) != 1 or x2.stride(0) % 8 != 0 or x2.stride(0) < K or x2.data_ptr() % 16 != 0:
-        x2 = x2.contiguous()
-    M = x2.shape[0]
-    # the table holds nothing but what its key says (a recycled address of an equal shape describes the same job)
-    key = tuple((w.data_ptr(), w.shape[0], w.stride(0), b.data_ptr() if b is not None else 0) for w, b in zip(weights, biases))
-    jobs = _group_jobs.get(key)
-    if jobs is None:
-        if len(_group_jobs) > 4096:
-            _group_jobs.clear()
-        jobs = _group_jobs[key] = (_lib.LinearJob * n)()
-        for g, (wp, N, ldw, bp) in enumerate(key):
-            jobs[g] = _lib.LinearJob(wp, bp or None, None, N, ldw, N)
-    outs = []
-    lead = x.shape[:-1]
-    for g in range(n):
-        y = torch.empty((M, key[g][1]), dtype=x.dtype, device=x.device)
-        jobs[g].Y = y.data_ptr()
-        outs.append(y)
-    _lib.check(_lib.load().vlmc_linear_fwd_group(x2.data_ptr(), jobs, n, _DT[x.dtype], M, K, x2.stride(0), _stream()))
-    return [y.reshape(*lead, y.shape[1]) for y in outs]
-
-
-def linear_fwd_rows(x: torch.Tensor, weights, biases, rowmap: torch.Tensor, n_real: int) -> list:
-    """[x @ w.T + b for w, b in zip(weights, biases)] over the rows `rowmap[:n_real]` of the flattened x only; rows
-    `rowmap[n_real:]` of every output are zeros (include/vlmc.h: vlmc_linear_fwd_rows).  x [.., K] flattens to M rows; `rowmap`:
-    int32 device tensor [M], a permutation of 0 .. M - 1 with the rows that are real first (a padded group of ragged calibration
-    samples: calibration.plan_padded builds it).  A computed row has the bits `linear_fwd` gives it."""
-    n = len(weights)
-    if biases is None:
-        biases = [None] * n
-    if _fast is not None and x.is_cuda and hasattr(_fast, "linear_fwd_rows"):
-        outs = _fast.linear_fwd_rows(x, list(weights), list(biases), rowmap, int(n_real), _stream())
-        if outs is not None:
-            return outs                                               # (None: not a call the kernel takes -- the checks below say why)
-    if not 1 <= n <= LINEAR_GROUP_MAX or len(biases) != n:
-        raise ValueError(f"linear_fwd_rows takes 1..{LINEAR_GROUP_MAX} weights and as many biases")
-    _need_gpu(x, rowmap, *weights, *[b for b in biases if b is not None])
-    f32 = x.dtype is torch.float32
-    for w, b in zip(weights, biases):
-        if not (linear_f32_supported(x, w, b) if f32 else linear_fwd_supported(x, w, b)):
-            raise TypeError("vlmc.linear_fwd_rows: fp16/bf16 tensors of one dtype with in_features % 8 == 0, or fp32 tensors, expected")
-    K = weights[0].shape[1]
-    x2 = x.reshape(-1, K)
-    if x2.stride(1) != 1 or x2.stride(0) < K or (not f32 and (x2.stride(0) % 8 != 0 or x2.data_ptr() % 16 != 0)):
-        x2 = x2.contiguous()
-    M = x2.shape[0]
-    if rowmap.dtype != torch.int32 or rowmap.dim() != 1 or rowmap.shape[0] != M or not rowmap.is_contiguous() or not 1 <= n_real <= M:
-        raise ValueError("vlmc.linear_fwd_rows: rowmap must be a contiguous int32 [rows of x] tensor and 1 <= n_real <= rows")
-    jobs = (_lib.LinearJob * n)()
-    outs = []
-    for g, (w, b) in enumerate(zip(weights, biases)):
-        y = torch.empty((M, w.shape[0]), dtype=x.dtype, device=x.device)
-        jobs[g] = _lib.LinearJob(w.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), w.shape[0], w.stride(0), w.shape[0])
-        outs.append(y)
-    _lib.check(_lib.load().vlmc_linear_fwd_rows(x2.data_ptr(), jobs, n, _DT[x.dtype], M, K, x2.stride(0), rowmap.data_ptr(), int(n_real),
-                                                _stream()))
-    lead = x.shape[:-1]
-    return [y.reshape(*lead, y.shape[1]) for y in outs]
-
-
-def linear_fwd_gather(x: torch.Tensor, weight: torch.Tensor, bias, x_rows: torch.Tensor, y_rows: torch.Tensor, n_real: int, out_rows: int,
-                      pitch: int) -> torch.Tensor:
-    """fp32: y[y_rows[i]] = x_base[x_rows[i]] @ weight.T + bias for i < n_real, y[y_rows[i]] = 0 for the other entries of y_rows;
-    y is a fresh [out_rows, N] tensor every row of which y_rows names once.  `x` is any fp32 CUDA tensor whose element (row r, k) lies
-    at x.data_ptr() + (r * pitch + k) * 4 for the rows x_rows names -- a token slice of a padded stack, read in place
-    (include/vlmc.h: vlmc_linear_fwd_gather).  A computed row has the bits `linear_fwd` gives it."""
-    _need_gpu(x, weight, x_rows, y_rows, *([bias] if bias is not None else []))
-    N, K = weight.shape
-    if x.dtype is not torch.float32 or weight.dtype is not torch.float32 or weight.stride(1) != 1 or weight.stride(0) < K or pitch < K or \
-            (bias is not None and (bias.dtype is not torch.float32 or not bias.is_contiguous() or bias.shape != (N,))):
-        raise TypeError("vlmc.linear_fwd_gather: fp32 x, weight [N, K] with contiguous rows and a contiguous fp32 bias expected")
-    for t, n_ in ((x_rows, n_real), (y_rows, out_rows)):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != n_:
-            raise ValueError("vlmc.linear_fwd_gather: x_rows int32 [n_real], y_rows int32 [out_rows], contiguous")
-    if not 0 <= n_real <= out_rows or out_rows < 1:
-        raise ValueError("vlmc.linear_fwd_gather: 0 <= n_real <= out_rows")
-    y = torch.empty((out_rows, N), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().vlmc_linear_fwd_gather(x.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None, _lib.F32, N, K,
-                                                  pitch, weight.stride(0), y.data_ptr(), N, x_rows.data_ptr(), y_rows.data_ptr(), int(n_real),
-                                                  int(out_rows - n_real), _stream()))
-    return y
-
-
-_16BIT = (torch.float16, torch.bfloat16)
 
 
 def attn_matmul_plan(a: torch.Tensor, b: torch.Tensor, _cuda_only: bool = True):
@@ -323,71 +167,6 @@ def attn_matmul_plan(a: torch.Tensor, b: torch.Tensor, _cuda_only: bool = True):
     return (batch, M, N, K, sab[0], sab[1], sa[-2], sbb[0], sbb[1], sbk, sbn)
 
 
-def attn_matmul(a: torch.Tensor, b: torch.Tensor, _plan=None, _try: bool = False) -> torch.Tensor:
-    """`torch.matmul(a, b)` for the batched products of attention (q @ k^T, attn @ v: eva_vit.py:147,164;
-    modeling_t5.py:590,638) on the batch-invariant MFMA kernel: an output element has the same bits whatever the batch
-    count, M or N (include/vlmc.h: vlmc_attn_matmul).  `_try`: None instead of an error for a call the kernel does not take.
-    fp32 operands (the reference's Q-Former): the fp32 matrix-core kernel, at most 65535 matrices per call."""
-    if a.dtype is torch.float32 and _fast is None:
-        plan = _plan if _plan is not None else attn_matmul_plan(a, b)
-        if plan is not None and plan[0][0] * plan[0][1] > 65535:
-            plan = None
-        if plan is None:
-            if _try:
-                return None
-            _need_gpu(a, b)
-            raise TypeError("vlmc.attn_matmul: 3-D / 4-D tensors of one dtype expected, a contiguous along k, b along k or n")
-        batch, M, N, K, sa0, sa1, sam, sb0, sb1, sbk, sbn = plan
-        out = torch.empty((*(batch if a.dim() == 4 else batch[1:]), M, N), dtype=a.dtype, device=a.device)
-        _lib.check(_lib.load().vlmc_attn_matmul(a.data_ptr(), b.data_ptr(), out.data_ptr(), _lib.F32, batch[0], batch[1], M, N, K, sa0, sa1, sam,
-                                                sb0, sb1, sbk, sbn, batch[1] * M * N, M * N, N, _stream()))
-        return out
-    if _fast is not None:
-        if not a.is_cuda:
-            if _try:
-                return None
-            _need_gpu(a, b)
-        out = _fast.attn_matmul(a, b, _stream())
-        if out is None and not _try:
-            _need_gpu(a, b)
-            raise TypeError("vlmc.attn_matmul: 3-D / 4-D fp16 / bf16 tensors of one dtype expected, a contiguous along k, b along k or n")
-        return out
-    plan = _plan if _plan is not None else attn_matmul_plan(a, b)
-    if plan is None:
-        if _try:
-            return None
-        _need_gpu(a, b)
-        raise TypeError("vlmc.attn_matmul: 3-D / 4-D fp16 / bf16 tensors of one dtype expected, a contiguous along k, b along k or n")
-    batch, M, N, K, sa0, sa1, sam, sb0, sb1, sbk, sbn = plan
-    nb0, nb1 = batch
-    out = torch.empty((*(batch if a.dim() == 4 else batch[1:]), M, N), dtype=a.dtype, device=a.device)
-    _lib.check(_lib.load().vlmc_attn_matmul(a.data_ptr(), b.data_ptr(), out.data_ptr(), _DT[a.dtype], nb0, nb1, M, N, K, sa0, sa1, sam,
-                                            sb0, sb1, sbk, sbn, nb1 * M * N, M * N, N, _stream()))
-    return out
-
-
-def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float, rsqrt_mode: int = 0) -> torch.Tensor:
-    """`weight * (x * rsqrt(x.float().pow(2).mean(-1, keepdim=True) + eps)).to(x.dtype)` -- T5LayerNorm / LlamaRMSNorm, op for op --
-    in one launch (include/vlmc.h: vlmc_rms_norm); the mean is `row_mean`'s.  16-bit CUDA x [.., n] and weight [n] of one dtype."""
-    _need_gpu(x, weight)
-    if _fast is not None and hasattr(_fast, "rms_norm"):
-        out = _fast.rms_norm(x, weight, float(eps), int(rsqrt_mode), _stream())
-        if out is None:
-            raise TypeError("vlmc.rms_norm: fp16 / bf16 x [.., n] and a contiguous weight [n] of the same dtype expected")
-        return out
-    n = x.shape[-1]
-    if x.dtype not in _16BIT or weight.dtype != x.dtype or weight.shape != (n,) or not weight.is_contiguous() or n == 0:
-        raise TypeError("vlmc.rms_norm: fp16 / bf16 x [.., n] and a contiguous weight [n] of the same dtype expected")
-    x2 = x.reshape(-1, n)
-    if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < n):
-        x2 = x2.contiguous()
-    rows = x2.shape[0]
-    out = torch.empty((rows, n), dtype=x.dtype, device=x.device)
-    _lib.check(_lib.load().vlmc_rms_norm(x2.data_ptr(), _DT[x.dtype], rows, n, x2.stride(0) if rows > 1 else n, weight.data_ptr(), float(eps),
-                                         int(rsqrt_mode), out.data_ptr(), n, _stream()))
-    return out.reshape(x.shape)
-
-
 _sdpa_max_keys = {}
 
 
@@ -412,57 +191,251 @@ def sdpa_plan(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
     return B, H, Tq, Tk, d
 
 
+def _members_fault(x, weights, biases, f32: bool):
+    """Why the linears of one launch are not a call the kernels take: ValueError for the member count, TypeError for the operands
+    (`f32`: the op takes fp32 members too); None when they are."""
+    if not 1 <= len(weights) <= LINEAR_GROUP_MAX or len(biases) != len(weights):
+        return ValueError
+    ok = linear_f32_supported if f32 and x.dtype is torch.float32 else linear_fwd_supported
+    return None if all(ok(x, w, b) for w, b in zip(weights, biases)) else TypeError
+
+
+def _rowmap_ok(rowmap, n_real, rows) -> bool:
+    return rowmap.is_cuda and rowmap.dtype == torch.int32 and rowmap.dim() == 1 and rowmap.shape[0] == rows and rowmap.is_contiguous() \
+        and 1 <= n_real <= rows
+
+
+_group_jobs = {}           # (W pointer, N, ldw, bias pointer) per member -> the launch's job table, everything but Y filled in
+
+
+def _job_table(x, rows, weights, biases):
+    """(table, outs): the `LinearJob` table of a group launch and its fresh outputs [rows, N].  The table holds nothing but what its
+    key says (a recycled address of an equal shape describes the same job) and Y, which every call sets."""
+    key = tuple((w.data_ptr(), w.shape[0], w.stride(0), b.data_ptr() if b is not None else 0) for w, b in zip(weights, biases))
+    jobs = _group_jobs.get(key)
+    if jobs is None:
+        if len(_group_jobs) > 4096:
+            _group_jobs.clear()
+        jobs = _group_jobs[key] = (_lib.LinearJob * len(key))(*(_lib.LinearJob(wp, bp or None, None, N, ldw, N) for wp, N, ldw, bp in key))
+    outs = [torch.empty((rows, k[1]), dtype=x.dtype, device=x.device) for k in key]
+    for job, y in zip(jobs, outs):
+        job.Y = y.data_ptr()
+    return jobs, outs
+
+
+class _ctypes_route:
+    """The ctypes back end: the entry points of `_FAST_ENTRY_POINTS` with the signatures and the contract of the compiled one
+    (vlmc/_fast) -- `op(tensors..., stream)` returns the result, or None when the call is not one the kernel takes; it raises for a
+    failed launch only, and the public op says what was wrong with a refused call.  Every launch here goes through it with
+    `VLMC_FAST=0`, with `VLMC_LIB`, and when _fast is not built; the tests hold the compiled route against it."""
+
+    @staticmethod
+    def linear_fwd(x, weight, bias, stream):
+        f32 = weight.dtype is torch.float32
+        if not (linear_f32_supported if f32 else linear_fwd_supported)(x, weight, bias):
+            return None
+        N, K = weight.shape
+        x2, M, ld = _rows(x, K, aligned=not f32)
+        y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+        _lib.check(_lib.load().vlmc_linear_fwd(x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None, _DT[x.dtype],
+                                               M, N, K, ld, weight.stride(0), y.data_ptr(), N, stream))
+        return y.reshape(*x.shape[:-1], N)
+
+    @staticmethod
+    def linear_fwd_group(x, weights, biases, stream):
+        if _members_fault(x, weights, biases, False) is not None:
+            return None
+        K = weights[0].shape[1]
+        x2, M, ld = _rows(x, K, aligned=True)
+        jobs, outs = _job_table(x, M, weights, biases)
+        _lib.check(_lib.load().vlmc_linear_fwd_group(x2.data_ptr(), jobs, len(outs), _DT[x.dtype], M, K, ld, stream))
+        return [y.reshape(*x.shape[:-1], y.shape[1]) for y in outs]
+
+    @staticmethod
+    def linear_fwd_rows(x, weights, biases, rowmap, n_real, stream):
+        if _members_fault(x, weights, biases, True) is not None:
+            return None
+        K = weights[0].shape[1]
+        x2, M, ld = _rows(x, K, aligned=x.dtype is not torch.float32)
+        if not _rowmap_ok(rowmap, n_real, M):
+            return None
+        jobs, outs = _job_table(x, M, weights, biases)
+        _lib.check(_lib.load().vlmc_linear_fwd_rows(x2.data_ptr(), jobs, len(outs), _DT[x.dtype], M, K, ld, rowmap.data_ptr(), n_real, stream))
+        return [y.reshape(*x.shape[:-1], y.shape[1]) for y in outs]
+
+    @staticmethod
+    def attn_matmul(a, b, stream):
+        plan = attn_matmul_plan(a, b)
+        if plan is None or (a.dtype is torch.float32 and plan[0][0] * plan[0][1] > 65535):      # (the fp32 kernel's matrices per call)
+            return None
+        (nb0, nb1), M, N, K, sa0, sa1, sam, sb0, sb1, sbk, sbn = plan
+        out = torch.empty((*((nb0, nb1) if a.dim() == 4 else (nb1,)), M, N), dtype=a.dtype, device=a.device)
+        _lib.check(_lib.load().vlmc_attn_matmul(a.data_ptr(), b.data_ptr(), out.data_ptr(), _DT[a.dtype], nb0, nb1, M, N, K, sa0, sa1, sam,
+                                                sb0, sb1, sbk, sbn, nb1 * M * N, M * N, N, stream))
+        return out
+
+    @staticmethod
+    def row_mean(x, keepdim, stream):
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() < 1 or x.shape[-1] == 0:
+            return None
+        x2, rows, ld = _rows(x, x.shape[-1])
+        out = torch.empty(x.shape[:-1] + ((1,) if keepdim else ()), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.load().vlmc_row_mean(x2.data_ptr(), rows, x.shape[-1], ld, out.data_ptr(), stream))
+        return out
+
+    @staticmethod
+    def rms_norm(x, weight, eps, rsqrt_mode, stream):
+        if not (x.is_cuda and weight.is_cuda) or x.dtype not in _16BIT or weight.dtype != x.dtype or x.dim() < 1 or \
+                weight.shape != x.shape[-1:] or not weight.is_contiguous() or x.shape[-1] == 0:
+            return None
+        n = x.shape[-1]
+        x2, rows, ld = _rows(x, n)
+        out = torch.empty((rows, n), dtype=x.dtype, device=x.device)
+        _lib.check(_lib.load().vlmc_rms_norm(x2.data_ptr(), _DT[x.dtype], rows, n, ld, weight.data_ptr(), eps, rsqrt_mode, out.data_ptr(), n, stream))
+        return out.reshape(x.shape)
+
+    @staticmethod
+    def sdpa(q, k, v, scale, causal, stream):
+        plan = sdpa_plan(q, k, v) if 0.0 < scale < 1e30 else None
+        if plan is None:
+            return None
+        B, H, Tq, Tk, d = plan
+        out = torch.empty((B, Tq, H, d), dtype=q.dtype, device=q.device)
+        sq, sk, sv = q.stride(), k.stride(), v.stride()
+        rc = _lib.load().vlmc_sdpa_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _DT[q.dtype], B, H, Tq, Tk, d,
+                                       sq[0], sq[1], sq[2], sk[0], sk[1], sk[2], sv[0], sv[1], sv[2], Tq * H * d, d, H * d, scale, int(causal), stream)
+        if rc == _lib.VLMC_EINVAL:                                       # the entry point refuses the call: not one the kernel takes (ADVICE r4)
+            return None
+        _lib.check(rc)
+        return out.transpose(1, 2)
+
+
+# What each op takes, said once: the text of its TypeError / ValueError.
+_EXPECTED = {
+    "linear_fwd": "fp16/bf16 x [.., K], weight [N, K] and bias of one dtype with in_features % 8 == 0, or fp32 ones, expected: weight rows "
+                  "contiguous (16-bit: 16-byte aligned), a contiguous bias",
+    "linear_fwd_group": f"1..{LINEAR_GROUP_MAX} weights and as many biases; fp16/bf16 tensors of one dtype with in_features % 8 == 0 expected",
+    "linear_fwd_rows": f"1..{LINEAR_GROUP_MAX} weights and as many biases; fp16/bf16 tensors of one dtype with in_features % 8 == 0, or fp32 "
+                       "tensors; rowmap a contiguous int32 [rows of x] tensor and 1 <= n_real <= rows expected",
+    "attn_matmul": "3-D / 4-D fp16 / bf16 / fp32 tensors of one dtype expected, a contiguous along k, b along k or n; fp32: at most 65535 matrices",
+    "row_mean": "a non-empty fp32 tensor expected",
+    "rms_norm": "fp16 / bf16 x [.., n] and a contiguous weight [n] of the same dtype expected",
+    "sdpa": "[B, H, T, d] fp16 / bf16 CUDA tensors of one dtype expected, d a multiple of 8 up to 128, unit stride along d, at most "
+            "vlmc_sdpa_max_keys(d) keys, a positive scale",
+}
+
+
+def _refuse(op: str, *tensors, fault=TypeError):
+    """Raise for a call that `op`'s back end did not take: RuntimeError for a tensor that is not on the GPU, else `fault`."""
+    _need_gpu(*tensors)
+    raise fault(f"vlmc.{op}: {_EXPECTED[op]}")
+
+
+def _refuse_linear(op: str, x, weights, biases, f32: bool, rowmap=None):
+    """The same for the linears: ValueError for the member count, TypeError for the operands, ValueError for what is left, the row map."""
+    _refuse(op, x, rowmap, *weights, *biases, fault=_members_fault(x, weights, biases, f32) or ValueError)
+
+
+def linear_fwd(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, _try: bool = False) -> torch.Tensor:
+    """y = x @ weight.T + bias on the batch-invariant MFMA kernel (`F.linear` inside the calibration replay's block
+    forwards, wanda_pruner.py:308-311,343-346): a row of y depends on its row of x only, whatever else is in the call.
+    `_try`: return None instead of raising when the call is not one the kernel takes.  fp32 tensors (the reference's Q-Former): the
+    fp32 matrix-core kernel, the same invariance."""
+    y = (_fast or _ctypes_route).linear_fwd(x, weight, bias, _stream()) if x.is_cuda else None
+    if y is None and not _try:
+        _refuse_linear("linear_fwd", x, [weight], [bias], True)
+    return y
+
+
+def linear_fwd_group(x: torch.Tensor, weights, biases=None) -> list:
+    """[x @ w.T + b for w, b in zip(weights, biases)] in ONE launch of the batch-invariant kernel: up to 4 linears fed the
+    same activations (q / k / v, wi_0 / wi_1, cross-attention k / v).  Every output has the bits `linear_fwd` gives it;
+    the launch shares the chip between the products (include/vlmc.h: vlmc_linear_fwd_group)."""
+    weights = list(weights)
+    biases = [None] * len(weights) if biases is None else list(biases)
+    outs = (_fast or _ctypes_route).linear_fwd_group(x, weights, biases, _stream()) if x.is_cuda else None
+    if outs is None:
+        _refuse_linear("linear_fwd_group", x, weights, biases, False)
+    return outs
+
+
+def linear_fwd_rows(x: torch.Tensor, weights, biases, rowmap: torch.Tensor, n_real: int) -> list:
+    """[x @ w.T + b for w, b in zip(weights, biases)] over the rows `rowmap[:n_real]` of the flattened x only; rows
+    `rowmap[n_real:]` of every output are zeros (include/vlmc.h: vlmc_linear_fwd_rows).  x [.., K] flattens to M rows; `rowmap`:
+    int32 device tensor [M], a permutation of 0 .. M - 1 with the rows that are real first (a padded group of ragged calibration
+    samples: calibration.plan_padded builds it).  A computed row has the bits `linear_fwd` gives it."""
+    weights = list(weights)
+    biases = [None] * len(weights) if biases is None else list(biases)
+    outs = (_fast or _ctypes_route).linear_fwd_rows(x, weights, biases, rowmap, int(n_real), _stream()) if x.is_cuda else None
+    if outs is None:
+        _refuse_linear("linear_fwd_rows", x, weights, biases, True, rowmap)
+    return outs
+
+
+def linear_fwd_gather(x: torch.Tensor, weight: torch.Tensor, bias, x_rows: torch.Tensor, y_rows: torch.Tensor, n_real: int, out_rows: int,
+                      pitch: int) -> torch.Tensor:
+    """fp32: y[y_rows[i]] = x_base[x_rows[i]] @ weight.T + bias for i < n_real, y[y_rows[i]] = 0 for the other entries of y_rows;
+    y is a fresh [out_rows, N] tensor every row of which y_rows names once.  `x` is any fp32 CUDA tensor whose element (row r, k) lies
+    at x.data_ptr() + (r * pitch + k) * 4 for the rows x_rows names -- a token slice of a padded stack, read in place
+    (include/vlmc.h: vlmc_linear_fwd_gather).  A computed row has the bits `linear_fwd` gives it."""
+    _need_gpu(x, weight, x_rows, y_rows, *([bias] if bias is not None else []))
+    N, K = weight.shape
+    if x.dtype is not torch.float32 or weight.dtype is not torch.float32 or weight.stride(1) != 1 or weight.stride(0) < K or pitch < K or \
+            (bias is not None and (bias.dtype is not torch.float32 or not bias.is_contiguous() or bias.shape != (N,))):
+        raise TypeError("vlmc.linear_fwd_gather: fp32 x, weight [N, K] with contiguous rows and a contiguous fp32 bias expected")
+    for t, n_ in ((x_rows, n_real), (y_rows, out_rows)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != n_:
+            raise ValueError("vlmc.linear_fwd_gather: x_rows int32 [n_real], y_rows int32 [out_rows], contiguous")
+    if not 0 <= n_real <= out_rows or out_rows < 1:
+        raise ValueError("vlmc.linear_fwd_gather: 0 <= n_real <= out_rows")
+    y = torch.empty((out_rows, N), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().vlmc_linear_fwd_gather(x.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None, _lib.F32, N, K,
+                                                  pitch, weight.stride(0), y.data_ptr(), N, x_rows.data_ptr(), y_rows.data_ptr(), int(n_real),
+                                                  int(out_rows - n_real), _stream()))
+    return y
+
+
+def attn_matmul(a: torch.Tensor, b: torch.Tensor, _plan=None, _try: bool = False) -> torch.Tensor:
+    """`torch.matmul(a, b)` for the batched products of attention (q @ k^T, attn @ v: eva_vit.py:147,164;
+    modeling_t5.py:590,638) on the batch-invariant MFMA kernel: an output element has the same bits whatever the batch
+    count, M or N (include/vlmc.h: vlmc_attn_matmul).  `_try`: None instead of an error for a call the kernel does not take.
+    fp32 operands (the reference's Q-Former): the fp32 matrix-core kernel, at most 65535 matrices per call.  (`_plan`: accepted,
+    unused -- the back end plans the call itself.)"""
+    out = (_fast or _ctypes_route).attn_matmul(a, b, _stream()) if a.is_cuda else None
+    if out is None and not _try:
+        _refuse("attn_matmul", a, b)
+    return out
+
+
+def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float, rsqrt_mode: int = 0) -> torch.Tensor:
+    """`weight * (x * rsqrt(x.float().pow(2).mean(-1, keepdim=True) + eps)).to(x.dtype)` -- T5LayerNorm / LlamaRMSNorm, op for op --
+    in one launch (include/vlmc.h: vlmc_rms_norm); the mean is `row_mean`'s.  16-bit CUDA x [.., n] and weight [n] of one dtype."""
+    out = (_fast or _ctypes_route).rms_norm(x, weight, float(eps), int(rsqrt_mode), _stream()) if x.is_cuda else None
+    if out is None:
+        _refuse("rms_norm", x, weight)
+    return out
+
+
 def sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale=None, _try: bool = False, causal: bool = False):
     """`F.scaled_dot_product_attention(q, k, v[, is_causal=True])` (no mask, no dropout) on the fused, batch-invariant MFMA kernel
     (include/vlmc.h: vlmc_sdpa_fwd).  The result is a [B, H, Tq, d] view of a [B, Tq, H, d] buffer: the `transpose(1, 2)
     .reshape(B, Tq, H * d)` that follows in every model file is then free.  LAYOUT CONTRACT: unlike torch's math path the
     result is NOT contiguous in [B, H, Tq, d] order -- code that goes on with `.view(B * H, Tq, d)` needs `.contiguous()` first
-    (`.reshape` and `.transpose(1, 2).reshape(...)` work as they are).  `_try`: None for a call the kernel does not take, also
-    when only the C entry point refuses it."""
-    if _fast is not None and q.is_cuda and hasattr(_fast, "sdpa"):
-        out = _fast.sdpa(q, k, v, float(q.shape[-1] ** -0.5 if scale is None else scale), bool(causal), _stream())
-        if out is None and not _try:
-            raise TypeError("vlmc.sdpa: [B, H, T, d] fp16 / bf16 CUDA tensors of one dtype expected, d a multiple of 8 up to 128, "
-                            "unit stride along d, at most vlmc_sdpa_max_keys(d) keys, a positive scale")
-        return out
-    plan = sdpa_plan(q, k, v) if (scale is None or 0.0 < float(scale) < float("inf")) else None
-    if plan is None:
-        if _try:
-            return None
-        _need_gpu(q, k, v)
-        raise TypeError("vlmc.sdpa: [B, H, T, d] fp16 / bf16 CUDA tensors of one dtype expected, d a multiple of 8 up to 128, "
-                        "unit stride along d, at most vlmc_sdpa_max_keys(d) keys")
-    B, H, Tq, Tk, d = plan
-    out = torch.empty((B, Tq, H, d), dtype=q.dtype, device=q.device)
-    sq, sk, sv = q.stride(), k.stride(), v.stride()
-    rc = _lib.load().vlmc_sdpa_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _DT[q.dtype], B, H, Tq, Tk, d,
-                                   sq[0], sq[1], sq[2], sk[0], sk[1], sk[2], sv[0], sv[1], sv[2], Tq * H * d, d, H * d,
-                                   float(d ** -0.5 if scale is None else scale), int(bool(causal)), _stream())
-    if rc:
-        if _try and rc == _lib.VLMC_EINVAL:                               # the entry point refuses the call: the caller's own op runs (ADVICE r4)
-            return None
-        _lib.check(rc)
-    return out.transpose(1, 2)
+    (`.reshape` and `.transpose(1, 2).reshape(...)` work as they are).  `_try`: None for a call the kernel does not take."""
+    out = None
+    if q.is_cuda:
+        out = (_fast or _ctypes_route).sdpa(q, k, v, float(q.shape[-1] ** -0.5 if scale is None else scale), bool(causal), _stream())
+    if out is None and not _try:
+        _refuse("sdpa", q, k, v)
+    return out
 
 
 def row_mean(x: torch.Tensor, keepdim: bool = False) -> torch.Tensor:
     """`x.mean(-1, keepdim=keepdim)` for fp32 CUDA tensors with a fixed, batch-invariant summation order (the norms of a
     replayed block: include/vlmc.h: vlmc_row_mean)."""
-    _need_gpu(x)
-    if _fast is not None:
-        out = _fast.row_mean(x, bool(keepdim), _stream())
-        if out is None:
-            raise TypeError("vlmc.row_mean: a non-empty fp32 tensor expected")
-        return out
-    if x.dtype != torch.float32 or x.dim() < 1 or x.shape[-1] == 0:
-        raise TypeError("vlmc.row_mean: a non-empty fp32 tensor expected")
-    n = x.shape[-1]
-    x2 = x.reshape(-1, n)
-    if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < n):
-        x2 = x2.contiguous()
-    rows = x2.shape[0]
-    out = torch.empty(x.shape[:-1] + ((1,) if keepdim else ()), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().vlmc_row_mean(x2.data_ptr(), rows, n, x2.stride(0) if rows > 1 else n, out.data_ptr(), _stream()))
+    out = (_fast or _ctypes_route).row_mean(x, bool(keepdim), _stream()) if x.is_cuda else None
+    if out is None:
+        _refuse("row_mean", x)
     return out
 
 
@@ -487,13 +460,9 @@ def softmax_rows(x: torch.Tensor, out_dtype=None) -> torch.Tensor:
                                                (x.dtype in _16BIT and out_dtype in (x.dtype, torch.float32))):
         raise TypeError("vlmc.softmax_rows: a non-empty fp32 tensor, or fp16 / bf16 with the same or fp32 output dtype, expected")
     n = x.shape[-1]
-    x2 = x.reshape(-1, n)
-    if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < n):
-        x2 = x2.contiguous()
-    rows = x2.shape[0]
+    x2, rows, ld = _rows(x, n)
     out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    _lib.check(_lib.load().vlmc_softmax_rows(x2.data_ptr(), _DT[x.dtype], rows, n, x2.stride(0) if rows > 1 else n, out.data_ptr(),
-                                             _DT[out_dtype], n, _stream()))
+    _lib.check(_lib.load().vlmc_softmax_rows(x2.data_ptr(), _DT[x.dtype], rows, n, ld, out.data_ptr(), _DT[out_dtype], n, _stream()))
     return out
 
 
@@ -721,10 +690,7 @@ def linear_fwd_24(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bia
         raise TypeError("vlmc.linear_fwd_24: fp16/bf16 x [.., K], contiguous values [N, K / 2] of the same dtype, meta [N, K / 8] uint8 "
                         "(K % 8 == 0) and a contiguous bias [N] of that dtype expected")
     N, K = values.shape[0], 2 * values.shape[1]
-    x2 = x.reshape(-1, K)
-    if x2.stride(1) != 1 or x2.stride(0) % 8 != 0 or x2.stride(0) < K or x2.data_ptr() % 16 != 0:
-        x2 = x2.contiguous()
-    M = x2.shape[0]
+    x2, M, ld = _rows(x, K, aligned=True)
     y = torch.empty((M, N), dtype=x.dtype, device=x.device)
     if M == 0:
         return y.reshape(*x.shape[:-1], N)
@@ -733,11 +699,11 @@ def linear_fwd_24(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bia
         dense = (N * K * 2 + 15) // 16 * 16
         ws = _linear24_ws.get(dense + 16, x.device)        # (the last 16 bytes: the unpack kernel's bad-group counter, unused)
         _lib.check(lib.vlmc_unpack_24(values.data_ptr(), meta.data_ptr(), dt, N, K, ws.data_ptr(), K, None, 0, ws.data_ptr() + dense, _stream()))
-        _lib.check(lib.vlmc_linear_fwd(x2.data_ptr(), ws.data_ptr(), bptr, dt, M, N, K, x2.stride(0), K, y.data_ptr(), N, _stream()))
+        _lib.check(lib.vlmc_linear_fwd(x2.data_ptr(), ws.data_ptr(), bptr, dt, M, N, K, ld, K, y.data_ptr(), N, _stream()))
         return y.reshape(*x.shape[:-1], N)
     nbytes = int(lib.vlmc_linear_fwd_24_workspace(M, N, K))
     ws = _linear24_ws.get(nbytes, x.device) if nbytes else None
-    _lib.check(lib.vlmc_linear_fwd_24(x2.data_ptr(), values.data_ptr(), meta.data_ptr(), bptr, dt, M, N, K, x2.stride(0), y.data_ptr(), N,
+    _lib.check(lib.vlmc_linear_fwd_24(x2.data_ptr(), values.data_ptr(), meta.data_ptr(), bptr, dt, M, N, K, ld, y.data_ptr(), N,
                                       ws.data_ptr() if ws is not None else None, nbytes, _stream()))
     return y.reshape(*x.shape[:-1], N)
 
