@@ -420,6 +420,55 @@ def test_fasterprune_with_one_launch_blocks_equals_the_multi_launch_route(groupe
         assert abs(float((wa == 0).float().mean()) - sp) < 0.01
 
 
+@pytest.mark.parametrize("grouped", [False, True])
+def test_sort_threshold_route_equals_the_select_route(grouped, monkeypatch):
+    """`VLMC_SGPT_SORT_THRESHOLD=1` -- the reference's own `torch.sort(tmp.flatten())[0][k]`, `tmp <= thresh` per linear
+    (sparsegpt_pruner.py:183-185) -- against the multi-tensor radix select, both with the sweep launched separately
+    (`VLMC_SGPT_SELECT_SWEEP=0`), through `fasterprune` per linear and through one `fasterprune_group`: weights, keep masks
+    (`mask_only`) and queued scores bit for bit.  in = 320: two full blocks and a 64-column tail; column 7 is dead; three scopes
+    of different heights and sparsities.  Every column holds distinct bf16 magnitudes, so scores tie in the dead column only
+    (all zero there, under every threshold)."""
+    from vlmc import sparsegpt as SG
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(1024, 320, generator=g)
+    x[:, 7] = 0
+    H = ((x.t() @ x) * (2.0 / 1024)).to(DEV)
+    outs, spars = (96, 64, 160), (0.5, 0.5, 0.3)
+    grid = torch.cat([(1 + torch.arange(128) / 128) * 2.0 ** -e for e in (4, 5, 6)])       # 384 magnitudes, exact in bf16
+    weights = []
+    for o in outs:
+        idx = torch.rand(320, 384, generator=g).argsort(1)[:, :o].t()                       # per column: o distinct ones
+        sign = (torch.rand(o, 320, generator=g) < 0.5).float() * 2 - 1
+        weights.append((grid[idx] * sign).contiguous().to(torch.bfloat16).to(DEV))
+    cache = {"rows_seen": 1024}
+    SG.factorize_many([(H, cache)])
+    assert int(cache["dead"].sum()) == 1
+    monkeypatch.setattr(SG, "_SELECT_SWEEP", False)
+
+    def run(select, mask_only):
+        monkeypatch.setattr(SG, "_SELECT_THRESHOLD", select)
+        lins = [nn.Linear(320, o, bias=False).to(DEV).to(torch.bfloat16) for o in outs]
+        for l, w in zip(lins, weights):
+            l.weight.data = w.clone()
+        sink = []
+        if grouped:
+            masks = SG.fasterprune_group(lins, list(spars), cache, score_sink=sink, mask_only=mask_only)
+        else:
+            masks = [SG.fasterprune(l, None, sp, factor_cache=cache, score_sink=sink, mask_only=mask_only) for l, sp in zip(lins, spars)]
+        return [l.weight.data for l in lins], masks, [s for _, s in sink]
+
+    for mask_only in (False, True):
+        (w_sel, m_sel, s_sel), (w_sort, m_sort, s_sort) = run(True, mask_only), run(False, mask_only)
+        for i, sp in enumerate(spars):
+            assert torch.equal(w_sel[i].view(torch.int16), w_sort[i].view(torch.int16))
+            assert torch.equal(s_sel[i], s_sort[i]) and not bool(torch.isnan(s_sel[i]))
+            if mask_only:
+                assert torch.equal(w_sel[i], weights[i]) and torch.equal(m_sel[i], m_sort[i])
+                assert abs(float((~m_sel[i]).float().mean()) - sp) < 0.01
+            else:
+                assert abs(float((w_sel[i] == 0).float().mean()) - sp) < 0.01
+
+
 # ---- round 4: the damping ROUTE held against the reference's own decision and against fp64 ---------------------------------
 def test_damping_route_on_the_goldens_is_the_references_and_fp64s():
     """sparsegpt_pruner.py:112-150 damps H only while its Cholesky fails.  On the reference's golden Hessians the route is

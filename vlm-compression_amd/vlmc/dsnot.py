@@ -161,15 +161,6 @@ def gather_stats(stats):
     return stats
 
 
-def _factor_budget(sizes, dev):
-    """Workgroups each persistent factorization launched together may take: the CUs shared in proportion to the tile counts,
-    at least 8 each (the rule of sparsegpt.factorize_many)."""
-    from .sparsegpt import _CHOL_NB
-    cus = torch.cuda.get_device_properties(dev).multi_processor_count
-    tot = sum((n // _CHOL_NB) ** 2 for n in sizes) or 1
-    return {n: max(8, min((n // _CHOL_NB) ** 2, (cus * (n // _CHOL_NB) ** 2) // tot)) for n in set(sizes)}
-
-
 @torch.no_grad()
 def sparsegpt_divisors(hessians, percdamp=0.01):
     """The divisor of DSnoT's SparseGPT initial metric for each Hessian of a block (dsnot_pruner.py:380-402): `dead = diag(H) == 0`,
@@ -186,8 +177,8 @@ def sparsegpt_divisors(hessians, percdamp=0.01):
     lib = _lib.load()
     main = torch.cuda.current_stream(dev)
     streams = sparsegpt.sweep_streams(dev) if len(hessians) > 1 else []
-    budget = _factor_budget([H.shape[0] for H in hessians], dev) if all(sparsegpt.persistent_factor_usable(H.shape[0])
-                                                                          for H in hessians) else {}
+    budget = sparsegpt.factor_budget([H.shape[0] for H in hessians], dev) if all(sparsegpt.persistent_factor_usable(H.shape[0])
+                                                                                  for H in hessians) else {}
     slots, out, bad = {}, [None] * len(hessians), []
     order = sorted(range(len(hessians)), key=lambda i: -hessians[i].shape[0])        # the largest chains first
     for j, i in enumerate(order):
