@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VLMC_ABI_VERSION 24
+#define VLMC_ABI_VERSION 25
 
 #define VLMC_OK 0
 #define VLMC_EINVAL (-1)     /* bad argument (shape, dtype, alignment, null pointer) */
@@ -233,6 +233,21 @@ int vlmc_pack_24(const void *W, int dtype, int64_t out_features, int64_t in_feat
 int vlmc_unpack_24(const void *values, const uint8_t *meta, int dtype, int64_t out_features, int64_t in_features, void *W, int64_t ldw,
                    uint8_t *mask /* NULL or [out, in] */, int64_t ldm, unsigned int *bad_groups, void *stream);
 
+/* ---- packed 4:8 weights (the reference's other n:m regime: prune_n = 4, prune_m = 8, wanda_pruner.py:326-329) ---------------------
+ * A linear whose mask keeps exactly four of every eight consecutive input columns as
+ *     values [out, in / 2]  16-bit, the four kept weights of every group of eight input columns, in column order
+ *     meta   [out, in / 8]  one byte per group: bit j is set exactly when column 8c + j is kept (popcount 4: 70 of the 256 values)
+ * 9 / 16 of the dense bytes, and the same chunk as the 2:4 format: 8 bytes of values + 1 byte of meta per 8 input columns.  The
+ * positions are the MASK's: vlmc_unpack_48(vlmc_pack_48(W, mask)) == W . mask bit for bit, the mask is recovered, a kept +0 / -0
+ * stays a kept zero.  Signatures and argument checks are those of vlmc_pack_24 / vlmc_unpack_24.  *bad_groups (device, zeroed by
+ * the caller) counts the groups of eight that do not keep exactly four (pack) or the metadata bytes whose popcount is not 4
+ * (unpack); their output is unspecified, and nothing outside the group is read or written for them.  Every 2:4 mask is also a
+ * 4:8 mask and is accepted here; a caller who wants the selector form of the 2:4 format calls vlmc_pack_24 first.               */
+int vlmc_pack_48(const void *W, int dtype, int64_t out_features, int64_t in_features, int64_t ldw, const uint8_t *mask, int64_t ldm,
+                 void *values, uint8_t *meta, unsigned int *bad_groups, void *stream);
+int vlmc_unpack_48(const void *values, const uint8_t *meta, int dtype, int64_t out_features, int64_t in_features, void *W, int64_t ldw,
+                   uint8_t *mask /* NULL or [out, in] */, int64_t ldm, unsigned int *bad_groups, void *stream);
+
 /* ---- a linear on the PACKED weight (inference: the rows of a generation step) ---------------------------------------------------
  *     Y[m, n] = wd(sum_k X[m, k] * W24[n, k] + bias[n])        W24 = vlmc_unpack_24(values, meta)
  * bit for bit what vlmc_linear_fwd gives on the unpacked weight (one accumulator per element over the K-steps of 32 in ascending
@@ -246,6 +261,14 @@ int vlmc_unpack_24(const void *values, const uint8_t *meta, int dtype, int64_t o
 int vlmc_linear_fwd_24_max_rows(void);
 size_t vlmc_linear_fwd_24_workspace(int64_t M, int64_t N, int64_t K);
 int vlmc_linear_fwd_24(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
+                       int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream);
+/* The same linear on the packed 4:8 weight (train.py:626-637, :677-714 at prune_n = 4, prune_m = 8): W48 = vlmc_unpack_48(values,
+ * meta) in place of W24, otherwise vlmc_linear_fwd_24's contract word for word -- the same kernel with another register expansion
+ * (a table of byte-permute selectors in LDS), bit for bit vlmc_linear_fwd on the unpacked weight.  meta is TRUSTED: a byte whose
+ * popcount is not 4 gives an unspecified product but never a read outside its own chunk (validate once with vlmc_unpack_48's
+ * bad_groups).  The row limit and the workspace are the same quantities for both formats: vlmc_linear_fwd_24_max_rows() and
+ * vlmc_linear_fwd_24_workspace() answer for this entry point too.                                                             */
+int vlmc_linear_fwd_48(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
                        int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- dense calibration forward of one linear (MFMA) ---------------------------------------------

@@ -1,7 +1,8 @@
-// A linear whose weight stays in the packed 2:4 format of pack24.hip (values [N, K / 2] + meta [N, K / 8], 9 / 16 of the dense
-// bytes), for the few rows of X a generation step brings (rows = batch x beams): there a linear costs the bytes of its weight.
+// A linear whose weight stays in the packed 2:4 format of pack24.hip or the packed 4:8 format of pack48.hip (both: values
+// [N, K / 2] + meta [N, K / 8], 9 / 16 of the dense bytes), for the few rows of X a generation step brings (rows = batch x beams):
+// there a linear costs the bytes of its weight.
 //
-//   Y[m][n] = wd(sum_k X[m][k] * W24[n][k] + bias[n])        W24 = unpack_24(values, meta)
+//   Y[m][n] = wd(sum_k X[m][k] * W24[n][k] + bias[n])        W24 = unpack_24(values, meta)   (or unpack_48: W48)
 //
 // BIT FOR BIT what vlmc_linear_fwd gives on the unpacked weight, because an output element is accumulated exactly as in
 // gemm_nt.hip: W rows are the A operand and X rows the B operand of v_mfma_f32_16x16x32_{f16,bf16}, a lane holds row lane & 15 and
@@ -11,7 +12,8 @@
 // layer gives.
 //
 // A lane's eight k of a K-step are one pack chunk -- 8 bytes of values and one byte of meta -- so the A fragment is expanded
-// lane-locally in registers and W never touches LDS; the B fragment is 16 contiguous bytes of a row of X (L2-resident: every
+// lane-locally in registers and W never touches LDS (what differs between the two formats is this expansion alone: Expand24 /
+// Expand48 below); the B fragment is 16 contiguous bytes of a row of X (L2-resident: every
 // workgroup reads all of X).  A workgroup owns 16 output features over all of K and keeps ceil(M / 16) accumulator tiles, so
 // the packed weight is read from memory once whatever M is.
 //
@@ -23,7 +25,7 @@
 // the same bits.
 //
 // M > vlmc_linear_fwd_24_max_rows() (prefill, the vision tower): compute-bound, so the entry point unpacks into the caller's
-// workspace (unpack24_kernel) and runs the dense launch -- the same bits by construction.
+// workspace (unpack24_kernel / unpack48_kernel) and runs the dense launch -- the same bits by construction.
 #include "common.hpp"
 #include "mfma.hpp"
 
@@ -61,8 +63,44 @@ __device__ __forceinline__ u32x4_t expand24(const u32x2_t v, const uint32_t code
     return w;
 }
 
-// MT tiles of 16 rows of X; D K-steps per batch (what a wave holds in registers)
-template <typename T, int MT>
+// The expansion policies: how one pack chunk (8 bytes of values, 1 byte of meta) becomes the 8 weights of the A fragment.
+// `init` runs once per workgroup before the kernel's first barrier.
+struct Expand24 {
+    __device__ __forceinline__ void init(int) {}
+    __device__ __forceinline__ u32x4_t operator()(const u32x2_t v, const uint32_t code) const { return expand24(v, code); }
+};
+
+// 4:8: bit j of the byte says that position j holds the next value.  The chunk's 8 bytes are exactly the sources of v_perm_b32
+// ({v[1], v[0]}: selector s picks byte s of the chunk, 0x0c gives 0x00), so each output dword is one perm whose selector comes
+// from a table byte -> four selector dwords (4 KiB of LDS, filled here).  A selector never names anything but a byte of the
+// chunk or zero, and the table is indexed by a byte: whatever the metadata holds, nothing outside the chunk is read.  A byte
+// with more than four bits set places the chunk's four values at its lowest four set bits and zeros at the others.
+struct Expand48 {
+    const u32x4_t *sel;
+    __device__ __forceinline__ void init(int tid) {
+        __shared__ u32x4_t table[256];
+        const uint32_t e = uint32_t(tid) >> 2, d = uint32_t(tid) & 3u;         // 64 * L24_WAVES threads = 256 entries x 4 dwords
+        uint32_t s = 0x0c0c0c0cu;
+#pragma unroll
+        for (uint32_t h = 0; h < 2; ++h) {
+            const uint32_t p = 2 * d + h, r = uint32_t(__popc(e & ((1u << p) - 1u)));   // position p takes value r
+            if (((e >> p) & 1u) && r < 4) s = (s & ~(0xffffu << (16 * h))) | ((2 * r) | (2 * r + 1) << 8) << (16 * h);
+        }
+        reinterpret_cast<uint32_t *>(table)[tid] = s;
+        sel = table;
+    }
+    __device__ __forceinline__ u32x4_t operator()(const u32x2_t v, const uint32_t code) const {
+        const u32x4_t s = sel[code & 0xffu];
+        u32x4_t w;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) w[d] = __builtin_amdgcn_perm(v[1], v[0], s[d]);
+        return w;
+    }
+};
+static_assert(64 * L24_WAVES == 256 * 4, "Expand48::init: one thread per selector dword");
+
+// MT tiles of 16 rows of X; D K-steps per batch (what a wave holds in registers); E the format's expansion
+template <typename T, int MT, typename E>
 __global__ __launch_bounds__(64 * L24_WAVES) void linear24_kernel(const Linear24Args a) {
     constexpr int D = MT == 1 ? 8 : (MT == 2 ? 4 : 2);
     __shared__ f32x4_t carry[MT][64];
@@ -71,6 +109,8 @@ __global__ __launch_bounds__(64 * L24_WAVES) void linear24_kernel(const Linear24
     const int fr = lane & 15, fq = lane >> 4;             // fragment: row (lane & 15), k = 8 * (lane >> 4) + j
     const int n0 = blockIdx.x * 16;
     const int chunks = a.K >> 3, nb = (chunks + 4 * D - 1) / (4 * D);
+    E expand;
+    expand.init(tid);
     if (tid == 0) turn = 0;
     __syncthreads();
 
@@ -114,7 +154,7 @@ __global__ __launch_bounds__(64 * L24_WAVES) void linear24_kernel(const Linear24
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             const bool ok = (b * D + d) * 4 + fq < chunks;
-            wf[d] = ok ? expand24(cur.v[d], cur.code[d]) : zero;
+            wf[d] = ok ? expand(cur.v[d], cur.code[d]) : zero;
 #pragma unroll
             for (int t = 0; t < MT; ++t) cur.x[t][d] = ok ? cur.x[t][d] : zero;
         }
@@ -156,13 +196,13 @@ __global__ __launch_bounds__(64 * L24_WAVES) void linear24_kernel(const Linear24
     }
 }
 
-template <typename T> static void launch_linear24(const Linear24Args &a, hipStream_t s) {
+template <typename T, typename E> static void launch_linear24(const Linear24Args &a, hipStream_t s) {
     const dim3 grid(unsigned((a.N + 15) / 16)), block(64 * L24_WAVES);
     switch ((a.M + 15) / 16) {
-        case 1: VLMC_LAUNCH_TIMED((linear24_kernel<T, 1>), grid, block, s, a); break;
-        case 2: VLMC_LAUNCH_TIMED((linear24_kernel<T, 2>), grid, block, s, a); break;
-        case 3: VLMC_LAUNCH_TIMED((linear24_kernel<T, 3>), grid, block, s, a); break;
-        default: VLMC_LAUNCH_TIMED((linear24_kernel<T, 4>), grid, block, s, a); break;
+        case 1: VLMC_LAUNCH_TIMED((linear24_kernel<T, 1, E>), grid, block, s, a); break;
+        case 2: VLMC_LAUNCH_TIMED((linear24_kernel<T, 2, E>), grid, block, s, a); break;
+        case 3: VLMC_LAUNCH_TIMED((linear24_kernel<T, 3, E>), grid, block, s, a); break;
+        default: VLMC_LAUNCH_TIMED((linear24_kernel<T, 4, E>), grid, block, s, a); break;
     }
 }
 
@@ -180,28 +220,43 @@ extern "C" size_t vlmc_linear_fwd_24_workspace(int64_t M, int64_t N, int64_t K) 
     return linear24_dense_bytes(N, K) + 16;
 }
 
-extern "C" int vlmc_linear_fwd_24(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
-                                  int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream) {
-    VLMC_REQUIRE(dtype == VLMC_F16 || dtype == VLMC_BF16, "vlmc_linear_fwd_24: dtype must be VLMC_F16 or VLMC_BF16");
-    VLMC_REQUIRE(X && values && meta && Y, "vlmc_linear_fwd_24: null pointer");
-    VLMC_REQUIRE(M > 0 && N > 0 && K > 0 && M < (int64_t(1) << 31) && N < (int64_t(1) << 31) && K < (int64_t(1) << 31),
-                 "vlmc_linear_fwd_24: bad shape");
+// the one entry point behind both formats: `fn` names the export in every error, `unpack` is the format's unpack export
+template <typename E>
+static int linear_packed_fwd(const char *fn, int (*unpack)(const void *, const uint8_t *, int, int64_t, int64_t, void *, int64_t, uint8_t *, int64_t,
+                                                           unsigned int *, void *),
+                             const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N, int64_t K,
+                             int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream) {
+    VLMC_REQUIRE(dtype == VLMC_F16 || dtype == VLMC_BF16, "%s: dtype must be VLMC_F16 or VLMC_BF16", fn);
+    VLMC_REQUIRE(X && values && meta && Y, "%s: null pointer", fn);
+    VLMC_REQUIRE(M > 0 && N > 0 && K > 0 && M < (int64_t(1) << 31) && N < (int64_t(1) << 31) && K < (int64_t(1) << 31), "%s: bad shape", fn);
     VLMC_REQUIRE(K % 8 == 0 && ldx % 8 == 0 && ldx >= K && ldy >= N,
-                 "vlmc_linear_fwd_24: K and the row stride of X must be multiples of 8 elements, ldx >= K, ldy >= N");
-    VLMC_REQUIRE(aligned16(X) && (reinterpret_cast<uintptr_t>(values) & 7u) == 0, "vlmc_linear_fwd_24: X must be 16-byte, values 8-byte aligned");
+                 "%s: K and the row stride of X must be multiples of 8 elements, ldx >= K, ldy >= N", fn);
+    VLMC_REQUIRE(aligned16(X) && (reinterpret_cast<uintptr_t>(values) & 7u) == 0, "%s: X must be 16-byte, values 8-byte aligned", fn);
     if (M > VLMC_LINEAR24_MAX_ROWS) {
         const size_t dense = linear24_dense_bytes(N, K);
         VLMC_REQUIRE(workspace != nullptr && workspace_bytes >= dense + 16 && aligned16(workspace),
-                     "vlmc_linear_fwd_24: M > %d needs a 16-byte aligned workspace of vlmc_linear_fwd_24_workspace() bytes", VLMC_LINEAR24_MAX_ROWS);
+                     "%s: M > %d needs a 16-byte aligned workspace of vlmc_linear_fwd_24_workspace() bytes", fn, VLMC_LINEAR24_MAX_ROWS);
         unsigned int *bad = reinterpret_cast<unsigned int *>(static_cast<unsigned char *>(workspace) + dense);
-        const int rc = vlmc_unpack_24(values, meta, dtype, N, K, workspace, K, nullptr, 0, bad, stream);
+        const int rc = unpack(values, meta, dtype, N, K, workspace, K, nullptr, 0, bad, stream);
         if (rc != VLMC_OK) return rc;
         return vlmc_linear_fwd(X, workspace, bias, dtype, M, N, K, ldx, K, Y, ldy, stream);
     }
     const Linear24Args a{static_cast<const uint16_t *>(X), static_cast<const uint16_t *>(values), meta, static_cast<const uint16_t *>(bias),
                          static_cast<uint16_t *>(Y), ldx, ldy, int(M), int(N), int(K)};
-    if (dtype == VLMC_BF16) launch_linear24<bf16_t>(a, as_stream(stream));
-    else launch_linear24<f16_t>(a, as_stream(stream));
-    VLMC_HIP_CHECK_LAUNCH("vlmc_linear_fwd_24");
+    if (dtype == VLMC_BF16) launch_linear24<bf16_t, E>(a, as_stream(stream));
+    else launch_linear24<f16_t, E>(a, as_stream(stream));
+    VLMC_HIP_CHECK_LAUNCH(fn);
     return VLMC_OK;
+}
+
+extern "C" int vlmc_linear_fwd_24(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
+                                  int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream) {
+    return linear_packed_fwd<Expand24>("vlmc_linear_fwd_24", vlmc_unpack_24, X, values, meta, bias, dtype, M, N, K, ldx, Y, ldy, workspace,
+                                       workspace_bytes, stream);
+}
+
+extern "C" int vlmc_linear_fwd_48(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
+                                  int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream) {
+    return linear_packed_fwd<Expand48>("vlmc_linear_fwd_48", vlmc_unpack_48, X, values, meta, bias, dtype, M, N, K, ldx, Y, ldy, workspace,
+                                       workspace_bytes, stream);
 }

@@ -13,7 +13,9 @@ Host-side file formats only: the tensors are whatever the pruners left on the GP
 Packed 2:4 (SURVEY.md §8(f)3 "an optional packed 2:4 format for inference"; the reference has none): `pack_state_dict_24` /
 `unpack_state_dict_24` turn the `weight` + `mask` pair of every linear that a 2:4 prune left behind into
 `weight_packed24` [out, in / 2] + `weight_meta24` [out, in / 8] (include/vlmc.h: vlmc_pack_24) and back, bit for bit --
-9 / 16 of the bytes of the 16-bit weight, 3 / 8 of weight + mask.
+9 / 16 of the bytes of the 16-bit weight, 3 / 8 of weight + mask.  Packed 4:8 (the reference's other n:m regime, prune_n = 4,
+prune_m = 8): `pack_state_dict_48` / `unpack_state_dict_48` / `load_packed_48`, the same functions over `weight_packed48` +
+`weight_meta48` (vlmc_pack_48: one byte per group of eight, bit j = column j kept), the same 9 / 16.
 """
 from __future__ import annotations
 
@@ -110,47 +112,78 @@ def remaining_proportion(model, orig_total_size) -> float:
 
 
 PACKED_VALUES, PACKED_META = "weight_packed24", "weight_meta24"
+PACKED_VALUES_48, PACKED_META_48 = "weight_packed48", "weight_meta48"
 
 
-def pack_state_dict_24(state: dict, keep_masks: bool = False) -> dict:
-    """`model.state_dict()` of a 2:4-pruned model with every (`<name>.weight`, `<name>.mask`) pair whose mask keeps exactly two of
-    every four input columns replaced by `<name>.weight_packed24` / `<name>.weight_meta24` (CUDA tensors; the kernels pack).
-    Pairs that are not 2:4 (unstructured masks, fp32 weights, widths that are not multiples of 8) stay as they are.
-    `keep_masks`: keep the `mask` entries of packed linears too (they are recoverable from the metadata)."""
-    from . import ops
+def _pack_state_dict(state: dict, keep_masks: bool, group: int, values_key: str, meta_key: str, pack) -> dict:
+    """every (`<name>.weight`, `<name>.mask`) pair whose mask keeps exactly group / 2 of every `group` input columns -> `pack`'s pair"""
     out = {}
     for k, v in state.items():
         if k.endswith(".weight") and k[:-6] + "mask" in state and isinstance(v, torch.Tensor) and v.is_cuda and v.dim() == 2 and \
                 v.dtype in (torch.float16, torch.bfloat16) and v.shape[1] % 8 == 0:
             m = state[k[:-6] + "mask"]
-            if m.shape == v.shape and m.dtype == torch.bool and bool((m.reshape(v.shape[0], -1, 4).sum(-1) == 2).all()):
+            if m.shape == v.shape and m.dtype == torch.bool and bool((m.reshape(v.shape[0], -1, group).sum(-1) == group // 2).all()):
                 w = v if v.stride(1) == 1 else v.contiguous()
                 # (what is stored is W . mask: under SparseLoRA the pruned positions of `weight` are zero already, lora.py:362)
-                values, meta = ops.pack_24(w, m if m.stride(1) == 1 else m.contiguous())
-                out[k[:-6] + PACKED_VALUES], out[k[:-6] + PACKED_META] = values, meta
+                values, meta = pack(w, m if m.stride(1) == 1 else m.contiguous())
+                out[k[:-6] + values_key], out[k[:-6] + meta_key] = values, meta
                 continue
         out[k] = v
     if not keep_masks:
-        for k in [k for k in out if k.endswith(".mask") and k[:-4] + PACKED_VALUES in out]:
+        for k in [k for k in out if k.endswith(".mask") and k[:-4] + values_key in out]:
             del out[k]
     return out
+
+
+def _unpack_state_dict(state: dict, device, values_key: str, meta_key: str, unpack) -> dict:
+    out = {}
+    for k, v in state.items():
+        if k.endswith("." + values_key):
+            base = k[:-len(values_key)]
+            values, meta = v, state[base + meta_key]
+            if device is not None:
+                values, meta = values.to(device), meta.to(device)
+            w, m = unpack(values.contiguous(), meta.contiguous())
+            out[base + "weight"], out[base + "mask"] = w, m
+        elif not k.endswith("." + meta_key):
+            out.setdefault(k, v)
+    return out
+
+
+def _load_packed(model, packed_state: dict, strict: bool, tag: str, values_key: str, meta_key: str, is_valid, cls):
+    """swap a `cls` in for every module whose `<name>.<values_key>` is in `packed_state` (metadata validated once), then load"""
+    state, fn = dict(packed_state), "load_packed_" + tag
+    for k in [k for k in state if k.endswith("." + values_key)]:
+        name = k[:-len(values_key) - 1]
+        values, meta = state[k], state.get(name + "." + meta_key)
+        if meta is None:
+            raise KeyError(f"{fn}: {name}.{meta_key} is missing")
+        if not is_valid(meta):
+            raise ValueError(f"{fn}: {name}.{meta_key} holds codes that pack_{tag} never writes")
+        old = model.get_submodule(name)
+        dev = next((t.device for t in list(old.parameters(recurse=False)) + list(old.buffers(recurse=False))), values.device)
+        bias = state.get(name + ".bias")
+        new = cls(torch.empty_like(values, device=dev), torch.empty_like(meta, device=dev), None if bias is None else torch.empty_like(bias, device=dev))
+        new.train(old.training)
+        parent, _, child = name.rpartition(".")
+        setattr(model.get_submodule(parent) if parent else model, child, new)
+        state.pop(name + ".mask", None)
+    return model.load_state_dict(state, strict=strict)
+
+
+def pack_state_dict_24(state: dict, keep_masks: bool = False) -> dict:
+    """`model.state_dict()` of a 2:4-pruned model with every (`<name>.weight`, `<name>.mask`) pair whose mask keeps exactly two of
+    every four input columns replaced by `<name>.weight_packed24` / `<name>.weight_meta24` (CUDA tensors; the kernels pack).
+    Pairs that are not 2:4 (unstructured masks, 4:8 masks, fp32 weights, widths that are not multiples of 8) stay as they are.
+    `keep_masks`: keep the `mask` entries of packed linears too (they are recoverable from the metadata)."""
+    from . import ops
+    return _pack_state_dict(state, keep_masks, 4, PACKED_VALUES, PACKED_META, ops.pack_24)
 
 
 def unpack_state_dict_24(state: dict, device=None) -> dict:
     """The dense state dict back: `<name>.weight` (zeros where nothing was kept) and `<name>.mask` for every packed pair."""
     from . import ops
-    out = {}
-    for k, v in state.items():
-        if k.endswith("." + PACKED_VALUES):
-            base = k[:-len(PACKED_VALUES)]
-            values, meta = v, state[base + PACKED_META]
-            if device is not None:
-                values, meta = values.to(device), meta.to(device)
-            w, m = ops.unpack_24(values.contiguous(), meta.contiguous())
-            out[base + "weight"], out[base + "mask"] = w, m
-        elif not k.endswith("." + PACKED_META):
-            out.setdefault(k, v)
-    return out
+    return _unpack_state_dict(state, device, PACKED_VALUES, PACKED_META, ops.unpack_24)
 
 
 def load_packed_24(model, packed_state: dict, strict: bool = True):
@@ -160,21 +193,26 @@ def load_packed_24(model, packed_state: dict, strict: bool = True):
     recoverable from the metadata and dropped.  Afterwards `model.state_dict()` is the packed state: it goes through
     `unpack_state_dict_24` / `pack_state_dict_24` bit for bit.  Returns `load_state_dict`'s result."""
     from . import packed24
-    state = dict(packed_state)
-    for k in [k for k in state if k.endswith("." + PACKED_VALUES)]:
-        name = k[:-len(PACKED_VALUES) - 1]
-        values, meta = state[k], state.get(name + "." + PACKED_META)
-        if meta is None:
-            raise KeyError(f"load_packed_24: {name}.{PACKED_META} is missing")
-        if not packed24.meta_24_is_valid(meta):
-            raise ValueError(f"load_packed_24: {name}.{PACKED_META} holds codes that pack_24 never writes")
-        old = model.get_submodule(name)
-        dev = next((t.device for t in list(old.parameters(recurse=False)) + list(old.buffers(recurse=False))), values.device)
-        bias = state.get(name + ".bias")
-        new = packed24.Linear24(torch.empty_like(values, device=dev), torch.empty_like(meta, device=dev),
-                                None if bias is None else torch.empty_like(bias, device=dev))
-        new.train(old.training)
-        parent, _, child = name.rpartition(".")
-        setattr(model.get_submodule(parent) if parent else model, child, new)
-        state.pop(name + ".mask", None)
-    return model.load_state_dict(state, strict=strict)
+    return _load_packed(model, packed_state, strict, "24", PACKED_VALUES, PACKED_META, packed24.meta_24_is_valid, packed24.Linear24)
+
+
+def pack_state_dict_48(state: dict, keep_masks: bool = False) -> dict:
+    """`pack_state_dict_24` for the 4:8 regime: every (`<name>.weight`, `<name>.mask`) pair whose mask keeps exactly four of every
+    eight input columns becomes `<name>.weight_packed48` / `<name>.weight_meta48` (include/vlmc.h: vlmc_pack_48), 9 / 16 of the
+    weight's bytes; every other pair stays as it is.  A 2:4 mask is also a 4:8 mask and is packed here: run `pack_state_dict_24`
+    first on a state dict whose 2:4 linears should get the 2:4 selector form."""
+    from . import ops
+    return _pack_state_dict(state, keep_masks, 8, PACKED_VALUES_48, PACKED_META_48, ops.pack_48)
+
+
+def unpack_state_dict_48(state: dict, device=None) -> dict:
+    """The dense state dict back: `<name>.weight` (zeros where nothing was kept) and `<name>.mask` for every packed 4:8 pair."""
+    from . import ops
+    return _unpack_state_dict(state, device, PACKED_VALUES_48, PACKED_META_48, ops.unpack_48)
+
+
+def load_packed_48(model, packed_state: dict, strict: bool = True):
+    """`load_packed_24` for what `pack_state_dict_48` made: the modules whose `<name>.weight_packed48` key is in `packed_state`
+    become `packed48.Linear48`, each `weight_meta48` validated once here (every byte has popcount 4; the kernels trust it)."""
+    from . import packed48
+    return _load_packed(model, packed_state, strict, "48", PACKED_VALUES_48, PACKED_META_48, packed48.meta_48_is_valid, packed48.Linear48)

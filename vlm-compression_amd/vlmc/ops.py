@@ -623,48 +623,78 @@ def rope_check(device=None):
     _lib.check(rc)
 
 
-def pack_24(weight: torch.Tensor, mask: torch.Tensor):
-    """(values [out, in / 2], meta [out, in / 8] uint8) of a 16-bit weight whose `mask` (bool, 1 = keep) keeps exactly two of every
-    four consecutive input columns (include/vlmc.h: vlmc_pack_24).  Raises if a group keeps another number."""
+# the two packed n:m formats (csrc/pack24.hip, csrc/pack48.hip): the same shapes, bytes and call sequences, so one body each for
+# pack / unpack / forward; what differs is the exports, the group a mask is held to and the words of the errors
+_FMT24 = dict(tag="24", nm="2:4", group="four", keep="two")
+_FMT48 = dict(tag="48", nm="4:8", group="eight", keep="four")
+
+
+def _pack_nm(f, weight, mask):
     _need_gpu(weight, mask)
     out_f, in_f = weight.shape
     if weight.dtype not in _16BIT or mask.shape != weight.shape or mask.dtype not in (torch.bool, torch.uint8) or in_f % 8 or \
             weight.stride(1) != 1 or mask.stride(1) != 1:
-        raise TypeError("vlmc.pack_24: a 16-bit weight [out, in] (in % 8 == 0) and a bool mask of the same shape, rows contiguous, expected")
+        raise TypeError(f"vlmc.pack_{f['tag']}: a 16-bit weight [out, in] (in % 8 == 0) and a bool mask of the same shape, rows contiguous, expected")
     values = torch.empty((out_f, in_f // 2), dtype=weight.dtype, device=weight.device)
     meta = torch.empty((out_f, in_f // 8), dtype=torch.uint8, device=weight.device)
     bad = torch.zeros(1, dtype=torch.int32, device=weight.device)
-    _lib.check(_lib.load().vlmc_pack_24(weight.data_ptr(), _DT[weight.dtype], out_f, in_f, weight.stride(0), mask.data_ptr(), mask.stride(0),
-                                        values.data_ptr(), meta.data_ptr(), bad.data_ptr(), _stream()))
+    pack = getattr(_lib.load(), "vlmc_pack_" + f["tag"])
+    _lib.check(pack(weight.data_ptr(), _DT[weight.dtype], out_f, in_f, weight.stride(0), mask.data_ptr(), mask.stride(0),
+                    values.data_ptr(), meta.data_ptr(), bad.data_ptr(), _stream()))
     n_bad = int(bad.item())
     if n_bad:
-        raise ValueError(f"vlmc.pack_24: {n_bad} groups of four columns do not keep exactly two weights: not a 2:4 mask")
+        raise ValueError(f"vlmc.pack_{f['tag']}: {n_bad} groups of {f['group']} columns do not keep exactly {f['keep']} weights: not a {f['nm']} mask")
     return values, meta
 
 
-def unpack_24(values: torch.Tensor, meta: torch.Tensor, want_mask: bool = True):
-    """The dense [out, in] weight (zeros where nothing was kept) and the bool mask of `pack_24`'s output (vlmc_unpack_24)."""
+def _unpack_nm(f, values, meta, want_mask):
     _need_gpu(values, meta)
     out_f, half = values.shape
     in_f = 2 * half
     if values.dtype not in _16BIT or meta.dtype != torch.uint8 or in_f % 8 or meta.shape != (out_f, in_f // 8) or \
             not values.is_contiguous() or not meta.is_contiguous():
-        raise TypeError("vlmc.unpack_24: contiguous values [out, in / 2] (16-bit) and meta [out, in / 8] (uint8) expected")
+        raise TypeError(f"vlmc.unpack_{f['tag']}: contiguous values [out, in / 2] (16-bit) and meta [out, in / 8] (uint8) expected")
     w = torch.empty((out_f, in_f), dtype=values.dtype, device=values.device)
     mask = torch.empty((out_f, in_f), dtype=torch.bool, device=values.device) if want_mask else None
     bad = torch.zeros(1, dtype=torch.int32, device=values.device)
-    _lib.check(_lib.load().vlmc_unpack_24(values.data_ptr(), meta.data_ptr(), _DT[values.dtype], out_f, in_f, w.data_ptr(), in_f,
-                                          None if mask is None else mask.data_ptr(), in_f, bad.data_ptr(), _stream()))
+    unpack = getattr(_lib.load(), "vlmc_unpack_" + f["tag"])
+    _lib.check(unpack(values.data_ptr(), meta.data_ptr(), _DT[values.dtype], out_f, in_f, w.data_ptr(), in_f,
+                      None if mask is None else mask.data_ptr(), in_f, bad.data_ptr(), _stream()))
     if int(bad.item()):
-        raise ValueError("vlmc.unpack_24: the metadata holds codes that pack_24 never writes")
+        raise ValueError(f"vlmc.unpack_{f['tag']}: the metadata holds codes that pack_{f['tag']} never writes")
     return w, mask
 
 
-_linear24_ws = Workspace()        # the dense weight of the unpack route: grows to the largest one seen, shared by every layer
+def pack_24(weight: torch.Tensor, mask: torch.Tensor):
+    """(values [out, in / 2], meta [out, in / 8] uint8) of a 16-bit weight whose `mask` (bool, 1 = keep) keeps exactly two of every
+    four consecutive input columns (include/vlmc.h: vlmc_pack_24).  Raises if a group keeps another number."""
+    return _pack_nm(_FMT24, weight, mask)
+
+
+def unpack_24(values: torch.Tensor, meta: torch.Tensor, want_mask: bool = True):
+    """The dense [out, in] weight (zeros where nothing was kept) and the bool mask of `pack_24`'s output (vlmc_unpack_24)."""
+    return _unpack_nm(_FMT24, values, meta, want_mask)
+
+
+def pack_48(weight: torch.Tensor, mask: torch.Tensor):
+    """(values [out, in / 2], meta [out, in / 8] uint8) of a 16-bit weight whose `mask` (bool, 1 = keep) keeps exactly four of every
+    eight consecutive input columns (include/vlmc.h: vlmc_pack_48; bit j of a metadata byte = column 8c + j is kept).  Raises if a
+    group keeps another number.  Every 2:4 mask is also a 4:8 mask and is accepted: a caller who wants the 2:4 selector form for
+    such linears runs `pack_24` first."""
+    return _pack_nm(_FMT48, weight, mask)
+
+
+def unpack_48(values: torch.Tensor, meta: torch.Tensor, want_mask: bool = True):
+    """The dense [out, in] weight (zeros where nothing was kept) and the bool mask of `pack_48`'s output (vlmc_unpack_48)."""
+    return _unpack_nm(_FMT48, values, meta, want_mask)
+
+
+_linear24_ws = Workspace()        # the dense weight of the unpack route: grows to the largest one seen, shared by every layer and both formats
 
 
 def linear_fwd_24_max_rows() -> int:
-    """Most rows of x the packed kernel itself takes (vlmc_linear_fwd_24_max_rows); above, `linear_fwd_24` unpacks into scratch."""
+    """Most rows of x the packed kernel itself takes (vlmc_linear_fwd_24_max_rows; the 2:4 and the 4:8 entry points share it);
+    above, `linear_fwd_24` / `linear_fwd_48` unpack into scratch."""
     return int(_lib.load().vlmc_linear_fwd_24_max_rows())
 
 
@@ -678,16 +708,16 @@ def linear_fwd_24_supported(x: torch.Tensor, values: torch.Tensor, meta: torch.T
             and (bias is None or (bias.is_cuda and bias.dtype == values.dtype and bias.is_contiguous() and bias.shape == (values.shape[0],))))
 
 
-def linear_fwd_24(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None,
-                  unpack: bool = False) -> torch.Tensor:
-    """y = x @ unpack_24(values, meta).T + bias computed FROM the packed weight (vlmc_linear_fwd_24): bit for bit
-    `linear_fwd(x, unpack_24(values, meta)[0], bias)`, any leading dims.  Up to `linear_fwd_24_max_rows()` rows one kernel reads
-    the packed bytes and expands them in registers; more rows (prefill) unpack into a per-device scratch weight and run the dense
-    kernel.  `meta` is trusted (`pack_24` wrote it, or `formats.load_packed_24` validated it).  `unpack`: the unpack route
-    whatever the number of rows (the cross-check of the packed kernel)."""
+def linear_fwd_48_supported(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None) -> bool:
+    """Whether `linear_fwd_48` takes this call: the shapes, dtypes and placement `linear_fwd_24_supported` asks for (the two
+    formats have the same tensors; only the meaning of a metadata byte differs)."""
+    return linear_fwd_24_supported(x, values, meta, bias)
+
+
+def _linear_fwd_nm(f, x, values, meta, bias, unpack):
     _need_gpu(x, values, meta, bias)
     if not linear_fwd_24_supported(x, values, meta, bias):
-        raise TypeError("vlmc.linear_fwd_24: fp16/bf16 x [.., K], contiguous values [N, K / 2] of the same dtype, meta [N, K / 8] uint8 "
+        raise TypeError(f"vlmc.linear_fwd_{f['tag']}: fp16/bf16 x [.., K], contiguous values [N, K / 2] of the same dtype, meta [N, K / 8] uint8 "
                         "(K % 8 == 0) and a contiguous bias [N] of that dtype expected")
     N, K = values.shape[0], 2 * values.shape[1]
     x2, M, ld = _rows(x, K, aligned=True)
@@ -698,14 +728,34 @@ def linear_fwd_24(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bia
     if unpack:
         dense = (N * K * 2 + 15) // 16 * 16
         ws = _linear24_ws.get(dense + 16, x.device)        # (the last 16 bytes: the unpack kernel's bad-group counter, unused)
-        _lib.check(lib.vlmc_unpack_24(values.data_ptr(), meta.data_ptr(), dt, N, K, ws.data_ptr(), K, None, 0, ws.data_ptr() + dense, _stream()))
+        _lib.check(getattr(lib, "vlmc_unpack_" + f["tag"])(values.data_ptr(), meta.data_ptr(), dt, N, K, ws.data_ptr(), K, None, 0,
+                                                           ws.data_ptr() + dense, _stream()))
         _lib.check(lib.vlmc_linear_fwd(x2.data_ptr(), ws.data_ptr(), bptr, dt, M, N, K, ld, K, y.data_ptr(), N, _stream()))
         return y.reshape(*x.shape[:-1], N)
     nbytes = int(lib.vlmc_linear_fwd_24_workspace(M, N, K))
     ws = _linear24_ws.get(nbytes, x.device) if nbytes else None
-    _lib.check(lib.vlmc_linear_fwd_24(x2.data_ptr(), values.data_ptr(), meta.data_ptr(), bptr, dt, M, N, K, ld, y.data_ptr(), N,
-                                      ws.data_ptr() if ws is not None else None, nbytes, _stream()))
+    _lib.check(getattr(lib, "vlmc_linear_fwd_" + f["tag"])(x2.data_ptr(), values.data_ptr(), meta.data_ptr(), bptr, dt, M, N, K, ld, y.data_ptr(), N,
+                                                           ws.data_ptr() if ws is not None else None, nbytes, _stream()))
     return y.reshape(*x.shape[:-1], N)
+
+
+def linear_fwd_24(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None,
+                  unpack: bool = False) -> torch.Tensor:
+    """y = x @ unpack_24(values, meta).T + bias computed FROM the packed weight (vlmc_linear_fwd_24): bit for bit
+    `linear_fwd(x, unpack_24(values, meta)[0], bias)`, any leading dims.  Up to `linear_fwd_24_max_rows()` rows one kernel reads
+    the packed bytes and expands them in registers; more rows (prefill) unpack into a per-device scratch weight and run the dense
+    kernel.  `meta` is trusted (`pack_24` wrote it, or `formats.load_packed_24` validated it).  `unpack`: the unpack route
+    whatever the number of rows (the cross-check of the packed kernel)."""
+    return _linear_fwd_nm(_FMT24, x, values, meta, bias, unpack)
+
+
+def linear_fwd_48(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None,
+                  unpack: bool = False) -> torch.Tensor:
+    """y = x @ unpack_48(values, meta).T + bias computed FROM the packed 4:8 weight (vlmc_linear_fwd_48): bit for bit
+    `linear_fwd(x, unpack_48(values, meta)[0], bias)`, any leading dims; `linear_fwd_24`'s routes, row limit
+    (`linear_fwd_24_max_rows()`) and scratch weight.  `meta` is trusted (`pack_48` wrote it, or `formats.load_packed_48`
+    validated it).  `unpack`: the unpack route whatever the number of rows (the cross-check of the packed kernel)."""
+    return _linear_fwd_nm(_FMT48, x, values, meta, bias, unpack)
 
 
 def hessian_accum(H: torch.Tensor, x: torch.Tensor, alpha: float, beta: float, rows=None) -> torch.Tensor:

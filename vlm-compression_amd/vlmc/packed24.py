@@ -24,19 +24,24 @@ def meta_24_is_valid(meta: torch.Tensor) -> bool:
     return bool((((m & 3) < ((m >> 2) & 3)) & (((m >> 4) & 3) < ((m >> 6) & 3))).all())
 
 
+def _mask_nm_from_zeros(weight: torch.Tensor, n: int, m: int, fn: str, words: tuple) -> torch.Tensor:
+    """the non-zeros of every group of `m` input columns, filled up with the lowest-index zero columns to exactly `n`"""
+    if weight.dim() != 2 or weight.shape[1] % m:
+        raise ValueError(f"{fn}: a weight [out, in] with in % {m} == 0 expected")
+    nz = (weight != 0).reshape(weight.shape[0], -1, m)
+    count = nz.sum(-1, keepdim=True)
+    bad = int((count > n).sum())
+    if bad:
+        raise ValueError(f"{fn}: {bad} groups of {words[1]} columns hold more than {words[0]} non-zero weights: not a {n}:{m} weight")
+    zero_rank = (~nz).cumsum(-1)                          # 1 for a group's first zero column, 2 for its second, ..
+    return (nz | (~nz & (zero_rank <= n - count))).reshape(weight.shape)
+
+
 def mask_24_from_zeros(weight: torch.Tensor) -> torch.Tensor:
     """A 2:4 mask for a weight whose masks were dropped and whose zeros were kept (the reference's reload, evaluate_new.py:226-276):
     per group of four input columns the non-zero ones, filled up with the lowest-index zero columns to exactly two.  Raises
     ValueError with the number of groups that hold more than two non-zeros."""
-    if weight.dim() != 2 or weight.shape[1] % 4:
-        raise ValueError("mask_24_from_zeros: a weight [out, in] with in % 4 == 0 expected")
-    nz = (weight != 0).reshape(weight.shape[0], -1, 4)
-    count = nz.sum(-1, keepdim=True)
-    bad = int((count > 2).sum())
-    if bad:
-        raise ValueError(f"mask_24_from_zeros: {bad} groups of four columns hold more than two non-zero weights: not a 2:4 weight")
-    zero_rank = (~nz).cumsum(-1)                          # 1 for a group's first zero column, 2 for its second, ..
-    return (nz | (~nz & (zero_rank <= 2 - count))).reshape(weight.shape)
+    return _mask_nm_from_zeros(weight, 2, 4, "mask_24_from_zeros", ("two", "four"))
 
 
 def is_mask_24(mask, shape) -> bool:
@@ -44,53 +49,56 @@ def is_mask_24(mask, shape) -> bool:
             and shape[1] % 8 == 0 and bool((mask.reshape(shape[0], -1, 4).sum(-1) == 2).all()))
 
 
-class Linear24(nn.Module):
-    """A linear whose weight exists only as `weight_packed24` [out, in / 2] + `weight_meta24` [out, in / 8] (buffers, the names of
-    `formats.pack_state_dict_24`) and a `bias` buffer.  `forward(x, dense=False)` takes the reference model files' call
-    `lin(x, dense)` (eva_vit.py:54-60)."""
+class _PackedLinear(nn.Module):
+    """What `Linear24` and `packed48.Linear48` share: everything but the buffer names and the three ops of the format."""
+    _VALUES = _META = _TAG = None                        # the state-dict names of the two buffers; "24" / "48": ops.pack_<tag>, ..
 
     def __init__(self, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None):
         super().__init__()
+        cls = type(self).__name__
         if values.dim() != 2 or values.dtype not in _16BIT or meta.dtype != torch.uint8 or values.shape[1] % 4 or \
                 tuple(meta.shape) != (values.shape[0], values.shape[1] // 4):
-            raise TypeError("Linear24: values [out, in / 2] (fp16 / bf16) and meta [out, in / 8] (uint8) expected")
+            raise TypeError(f"{cls}: values [out, in / 2] (fp16 / bf16) and meta [out, in / 8] (uint8) expected")
         if bias is not None and (bias.dtype != values.dtype or tuple(bias.shape) != (values.shape[0],)):
-            raise TypeError("Linear24: a bias [out] of the values' dtype expected")
+            raise TypeError(f"{cls}: a bias [out] of the values' dtype expected")
         self.out_features, self.in_features = values.shape[0], 2 * values.shape[1]
-        self.register_buffer(PACKED_VALUES, values.detach().contiguous())
-        self.register_buffer(PACKED_META, meta.contiguous())
+        self.register_buffer(self._VALUES, values.detach().contiguous())
+        self.register_buffer(self._META, meta.contiguous())
         self.register_buffer("bias", None if bias is None else bias.detach().contiguous())
+
+    @classmethod
+    def _op(cls, name: str):
+        from . import ops
+        return getattr(ops, f"{name}_{cls._TAG}")
 
     @property
     def dtype(self):
-        return getattr(self, PACKED_VALUES).dtype
+        return getattr(self, self._VALUES).dtype
 
     def extra_repr(self):
         return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, dtype={self.dtype}"
 
     def forward(self, x: torch.Tensor, dense: bool = False) -> torch.Tensor:
-        from . import ops
+        cls = type(self).__name__
         if dense:
-            raise RuntimeError("Linear24: dense=True asks for the unpruned weight, which a packed linear no longer has")
+            raise RuntimeError(f"{cls}: dense=True asks for the unpruned weight, which a packed linear no longer has")
         if x.requires_grad and torch.is_grad_enabled():
-            raise RuntimeError("Linear24 is inference only: its input requires a gradient")
+            raise RuntimeError(f"{cls} is inference only: its input requires a gradient")
         if x.dtype != self.dtype:
-            raise TypeError(f"Linear24: input of dtype {x.dtype}, weights packed as {self.dtype}")
-        return ops.linear_fwd_24(x, getattr(self, PACKED_VALUES), getattr(self, PACKED_META), self.bias)
+            raise TypeError(f"{cls}: input of dtype {x.dtype}, weights packed as {self.dtype}")
+        return self._op("linear_fwd")(x, getattr(self, self._VALUES), getattr(self, self._META), self.bias)
 
     @classmethod
-    def from_linear(cls, module: nn.Module, mask: torch.Tensor | None = None) -> "Linear24":
+    def from_linear(cls, module: nn.Module, mask: torch.Tensor | None = None):
         """Pack `module.weight . mask` (`mask`: the module's own `mask` by default) on the GPU."""
-        from . import ops
         mask = module.mask if mask is None else mask
         w = module.weight.detach()
-        values, meta = ops.pack_24(w if w.stride(1) == 1 else w.contiguous(), mask if mask.stride(1) == 1 else mask.contiguous())
+        values, meta = cls._op("pack")(w if w.stride(1) == 1 else w.contiguous(), mask if mask.stride(1) == 1 else mask.contiguous())
         return cls(values, meta, None if module.bias is None else module.bias.detach())
 
     def to_linear(self) -> nn.Linear:
         """The dense `nn.Linear` back: weight W . mask, the `mask` attribute a prune leaves (wanda_pruner.py:339)."""
-        from . import ops
-        w, mask = ops.unpack_24(getattr(self, PACKED_VALUES), getattr(self, PACKED_META))
+        w, mask = self._op("unpack")(getattr(self, self._VALUES), getattr(self, self._META))
         lin = nn.Linear(self.in_features, self.out_features, bias=self.bias is not None, device="meta")
         lin.weight = nn.Parameter(w, requires_grad=False)
         if self.bias is not None:
@@ -99,14 +107,22 @@ class Linear24(nn.Module):
         return lin.train(self.training)
 
 
+class Linear24(_PackedLinear):
+    """A linear whose weight exists only as `weight_packed24` [out, in / 2] + `weight_meta24` [out, in / 8] (buffers, the names of
+    `formats.pack_state_dict_24`) and a `bias` buffer.  `forward(x, dense=False)` takes the reference model files' call
+    `lin(x, dense)` (eva_vit.py:54-60)."""
+    _VALUES, _META, _TAG = PACKED_VALUES, PACKED_META, "24"
+
+
 def _empty_adapter(m) -> bool:
     """A SparseLoRA `Linear` whose adapter adds nothing: r == 0, merged, or lora_B all zero (what `merge()` leaves, lora.py:384-394)."""
     return m.r == 0 or m.merged or not bool(m.lora_B.weight.any())
 
 
-def _packable(m, from_zeros: bool):
-    """The 2:4 mask under which module `m` can be replaced, or None."""
+def _packable(m, from_zeros: bool, is_mask=None, mask_from_zeros=None):
+    """The n:m mask under which module `m` can be replaced, or None (`is_mask`, `mask_from_zeros`: the format's; 2:4 by default)."""
     from lavis.peft.src.peft.tuners.lora import Linear as LoraLinear
+    is_mask, mask_from_zeros = is_mask or is_mask_24, mask_from_zeros or mask_24_from_zeros
     if type(m) is nn.Linear:
         pass
     elif type(m) is LoraLinear:
@@ -119,10 +135,10 @@ def _packable(m, from_zeros: bool):
         return None
     mask = getattr(m, "mask", None)
     if torch.is_tensor(mask):
-        return mask if is_mask_24(mask, w.shape) else None
+        return mask if is_mask(mask, w.shape) else None
     if from_zeros and type(m) is nn.Linear:
         try:
-            return mask_24_from_zeros(w.detach())
+            return mask_from_zeros(w.detach())
         except ValueError:
             return None
     return None
@@ -133,29 +149,37 @@ def _replace(model: nn.Module, name: str, new: nn.Module):
     setattr(model.get_submodule(parent_name) if parent_name else model, child, new)
 
 
-def pack_model_24_(model: nn.Module, from_zeros: bool = False) -> list:
-    """Replace, in place, every `nn.Linear` (exact type) that carries a 2:4 `mask` attribute, and every SparseLoRA `Linear` with
-    `sparse=True` and an empty adapter, by a `Linear24`.  `from_zeros`: also a plain linear without a mask whose zeros allow a 2:4
-    one (`mask_24_from_zeros`).  fp32 linears and masks that are not 2:4 stay as they are.  Returns the names replaced."""
+def _pack_model_(model: nn.Module, cls, from_zeros: bool, is_mask=None, mask_from_zeros=None) -> list:
     done = []
     for name, m in list(model.named_modules()):
         if not name:
             continue
-        mask = _packable(m, from_zeros)
+        mask = _packable(m, from_zeros, is_mask, mask_from_zeros)
         if mask is None:
             continue
-        new = Linear24.from_linear(m, mask)
+        new = cls.from_linear(m, mask)
         new.train(m.training)
         _replace(model, name, new)
         done.append(name)
     return done
 
 
-def unpack_model_24_(model: nn.Module) -> list:
-    """Replace every `Linear24` by its dense `nn.Linear` (`to_linear`).  Returns the names replaced."""
+def _unpack_model_(model: nn.Module, cls) -> list:
     done = []
     for name, m in list(model.named_modules()):
-        if name and isinstance(m, Linear24):
+        if name and isinstance(m, cls):
             _replace(model, name, m.to_linear())
             done.append(name)
     return done
+
+
+def pack_model_24_(model: nn.Module, from_zeros: bool = False) -> list:
+    """Replace, in place, every `nn.Linear` (exact type) that carries a 2:4 `mask` attribute, and every SparseLoRA `Linear` with
+    `sparse=True` and an empty adapter, by a `Linear24`.  `from_zeros`: also a plain linear without a mask whose zeros allow a 2:4
+    one (`mask_24_from_zeros`).  fp32 linears and masks that are not 2:4 stay as they are.  Returns the names replaced."""
+    return _pack_model_(model, Linear24, from_zeros)
+
+
+def unpack_model_24_(model: nn.Module) -> list:
+    """Replace every `Linear24` by its dense `nn.Linear` (`to_linear`).  Returns the names replaced."""
+    return _unpack_model_(model, Linear24)
