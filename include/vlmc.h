@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VLMC_ABI_VERSION 25
+#define VLMC_ABI_VERSION 26
 
 #define VLMC_OK 0
 #define VLMC_EINVAL (-1)     /* bad argument (shape, dtype, alignment, null pointer) */
@@ -270,6 +270,42 @@ int vlmc_linear_fwd_24(const void *X, const void *values, const uint8_t *meta, c
  * vlmc_linear_fwd_24_workspace() answer for this entry point too.                                                             */
 int vlmc_linear_fwd_48(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
                        int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- packed UNSTRUCTURED weights, "bm" (any mask: what the unstructured branch of every pruner leaves, wanda_pruner.py:330-337, and
+ * the `mask` a prune puts on a module, :339; the reference has no packed format) -------------------------------------------------
+ * A 16-bit weight [out, in] (in % 8 == 0, in <= 65536) under a bool mask with nnz kept positions, S = ceil(in / 32):
+ *     values [nnz + 16]       the kept weights, row after row in column order, then 16 zeros of tail
+ *     meta   [out, in / 8]    bit j of byte c is set exactly when column 8c + j is kept (the 4:8 byte without the popcount rule)
+ *     offs   [out, S] uint16  offs[n][s] = the number of kept columns of row n before column 32 s
+ *     rowptr [out + 1] int64  rowptr[n] = the index in values of row n's first kept weight, rowptr[out] == nnz
+ * The first value of chunk c of row n (s = c / 4, q = c % 4) is at rowptr[n] + offs[n][s] + popcount(meta[n][4s .. 4s+q-1]).
+ * (16 d + 1.5) / 16 of the dense bytes at kept density d, plus 8 (out + 1) + 32.  The positions are the MASK's:
+ * vlmc_unpack_bm(vlmc_pack_bm(W, mask)) == W . mask bit for bit, the mask is recovered, a kept +0 / -0 stays a kept zero.
+ * vlmc_pack_bm_rows: mask -> rowptr (count per row, exclusive scan on the device); the caller reads rowptr[out] once to size values.
+ * vlmc_pack_bm: W, mask, that rowptr and nnz = rowptr[out] -> values (nothing outside [0, nnz + 16) is written), meta, offs.
+ * vlmc_unpack_bm: -> W and an optional mask.  *bad (device, zeroed by the caller) counts the steps whose offs and the rows whose
+ * rowptr disagree with the bitmap's running popcount (rowptr[0] != 0 and rowptr[out] != nnz included); their output is unspecified,
+ * and whatever the metadata holds nothing outside values[0, nnz + 16) is read (the computed index is clamped to [0, nnz]).
+ * Argument checks are those of vlmc_pack_48 / vlmc_unpack_48, and in_features <= 65536.                                       */
+int vlmc_pack_bm_rows(const uint8_t *mask, int64_t ldm, int64_t out_features, int64_t in_features, int64_t *rowptr, void *stream);
+int vlmc_pack_bm(const void *W, int dtype, int64_t out_features, int64_t in_features, int64_t ldw, const uint8_t *mask, int64_t ldm,
+                 const int64_t *rowptr, int64_t nnz, void *values, uint8_t *meta, uint16_t *offs, void *stream);
+int vlmc_unpack_bm(const void *values, const uint8_t *meta, const uint16_t *offs, const int64_t *rowptr, int64_t nnz, int dtype,
+                   int64_t out_features, int64_t in_features, void *W, int64_t ldw, uint8_t *mask /* NULL or [out, in] */, int64_t ldm,
+                   unsigned int *bad, void *stream);
+/* The linear of vlmc_linear_fwd_24 on the bm weight: Wbm = vlmc_unpack_bm(values, meta, offs, rowptr, nnz) in place of W24, bit for
+ * bit vlmc_linear_fwd on the unpacked weight -- the same kernel with a third register expansion that brings its own loads.  X
+ * 16-byte aligned, values and meta 4-byte aligned (both are read in aligned dwords: of meta's last dword up to three bytes past its
+ * end, never used), K <= 65536.  meta, offs and rowptr are TRUSTED (validate once with vlmc_unpack_bm's bad); the index into
+ * values is clamped to [0, nnz] all the same, so that nothing outside values[0, nnz + 16) is read.  The format has its OWN row limit,
+ * vlmc_linear_fwd_bm_max_rows() (a multiple of 16 in 16..64); above it the weight is unpacked into `workspace`
+ * (vlmc_linear_fwd_bm_workspace() bytes: the quantity vlmc_linear_fwd_24_workspace reports, above this limit) and the dense kernel
+ * runs.                                                                                                                          */
+int vlmc_linear_fwd_bm_max_rows(void);
+size_t vlmc_linear_fwd_bm_workspace(int64_t M, int64_t N, int64_t K);
+int vlmc_linear_fwd_bm(const void *X, const void *values, const uint8_t *meta, const uint16_t *offs, const int64_t *rowptr, int64_t nnz,
+                       const void *bias, int dtype, int64_t M, int64_t N, int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace,
+                       size_t workspace_bytes, void *stream);
 
 /* ---- dense calibration forward of one linear (MFMA) ---------------------------------------------
  * Replaces `F.linear(x, weight, bias)` inside the block forwards of the calibration replay,

@@ -1,4 +1,5 @@
-"""The packed 2:4 linear (vlmc_linear_fwd_24) or, with `--format 48`, the packed 4:8 linear (vlmc_linear_fwd_48) against the dense
+"""The packed 2:4 linear (vlmc_linear_fwd_24), with `--format 48` the packed 4:8 linear (vlmc_linear_fwd_48), or with `--format bm` the
+bitmap-packed linear of an UNSTRUCTURED prune (vlmc_linear_fwd_bm; `--density` of every row kept, 0.5 by default) against the dense
 kernel (vlmc_linear_fwd on the unpacked weight) at the LLM shapes of Vicuna-7B and FlanT5-XL, fp16, COLD weights: every timed call
 takes the next of a pool of weight copies, and a round over the pool
 holds more than twice the 256 MiB Infinity Cache for the packed set and the dense set alike (one packed Vicuna layer is 228 MB
@@ -10,8 +11,9 @@ Two clocks, both on the device:
            gaps included; this is the only clock that sees the two kernels of the unpack route (unpack into scratch + dense)
 Every row is measured `--repeats` times with the routes alternating; the table prints the median and the spread (max - min).
 
-    python tools/bench_linear24.py [--format 24|48] [--only v7b] [--rows 1,8,16] [--repeats 3] [--out profiles/linear24.md]
-(`--format 48 --rows 1,2,4,8,16,32,48,64,128 --out <file>` gives the table of profiles/linear48.md)"""
+    python tools/bench_linear24.py [--format 24|48|bm] [--density 0.5] [--only v7b] [--rows 1,8,16] [--repeats 3] [--out profiles/linear24.md]
+(`--format 48 --rows 1,2,4,8,16,32,48,64,128 --out <file>` gives the table of profiles/linear48.md; `--format bm --out <file>` that of
+profiles/linearbm.md, measured on a build whose VLMC_LINEARBM_MAX_ROWS is 64 so that the packed kernel is timed at every candidate limit)"""
 import argparse
 import os
 import statistics
@@ -85,14 +87,16 @@ def main():
     ap.add_argument("--rows", default=",".join(map(str, ROWS)))
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default="")
-    ap.add_argument("--format", default="24", choices=("24", "48"), help="the packed format: 2:4 selectors or 4:8 bit masks")
+    ap.add_argument("--format", default="24", choices=("24", "48", "bm"), help="the packed format: 2:4 selectors, 4:8 bit masks or the bitmap of any mask")
+    ap.add_argument("--density", type=float, default=0.5, help="--format bm: the share of every row's columns that is kept")
     args = ap.parse_args()
     n_keep, n_of = (2, 4) if args.format == "24" else (4, 8)
     pack, packed_fwd = getattr(ops, "pack_" + args.format), getattr(ops, "linear_fwd_" + args.format)
     assert torch.cuda.is_available(), "bench_linear24.py measures on the GPU only"
     rows = [int(r) for r in args.rows.split(",")]
-    max_rows = ops.linear_fwd_24_max_rows()
-    lines = [f"format {n_keep}:{n_of} (`vlmc_linear_fwd_{args.format}`); max_rows of this build: {max_rows}; fp16; median of {args.repeats} (spread = max - min); "
+    max_rows = ops.linear_fwd_bm_max_rows() if args.format == "bm" else ops.linear_fwd_24_max_rows()
+    what = f"unstructured, {args.density:g} of every row kept" if args.format == "bm" else f"{n_keep}:{n_of}"
+    lines = [f"format {what} (`vlmc_linear_fwd_{args.format}`); max_rows of this build: {max_rows}; fp16; median of {args.repeats} (spread = max - min); "
              "GB/s = weight bytes of the route / kernel time",
              "",
              "| shape (N x K) | M | packed kernel us (spread) | GB/s | dense kernel us (spread) | GB/s | packed / dense | "
@@ -104,17 +108,21 @@ def main():
             continue
         g = torch.Generator(device=DEV).manual_seed(0)
         W = (torch.randn(N, K, device=DEV, generator=g) * 0.02).half()
-        keep, _ = ops.wanda_select(W, torch.rand(K, device=DEV, generator=g) + 0.5, "nm", n=n_keep, m=n_of)
-        values, meta = pack(W, keep)
-        packed_bytes, dense_bytes = values.numel() * 2 + meta.numel(), W.numel() * 2
-        pool = 2 * CACHE // packed_bytes + 1           # a round of the SMALLER set still holds more than twice the cache
-        Vs, Ms, Ws = [values.clone() for _ in range(pool)], [meta.clone() for _ in range(pool)], [W.clone() for _ in range(pool)]
+        sq = torch.rand(K, device=DEV, generator=g) + 0.5
+        if args.format == "bm":
+            keep, _ = ops.wanda_select(W, sq, "row", k=K - int(round(K * args.density)))
+        else:
+            keep, _ = ops.wanda_select(W, sq, "nm", n=n_keep, m=n_of)
+        packed = pack(W, keep)                         # (values, meta) or (values, meta, offs, rowptr)
+        packed_bytes, dense_bytes = sum(t.numel() * t.element_size() for t in packed), W.numel() * 2
+        pool = 2 * CACHE // min(packed_bytes, dense_bytes) + 1   # a round of the SMALLER set still holds more than twice the cache
+        Ps, Ws = [tuple(t.clone() for t in packed) for _ in range(pool)], [W.clone() for _ in range(pool)]
         del keep
         for M in rows:
             x = torch.randn(M, K, device=DEV, generator=g).half()
             want = ops.linear_fwd(x, W)
-            assert torch.equal(packed_fwd(x, values, meta).view(torch.int16), want.view(torch.int16)), (name, M)
-            calls = {"packed": lambda i: packed_fwd(x, Vs[i], Ms[i]), "unpack": lambda i: packed_fwd(x, Vs[i], Ms[i], unpack=True),
+            assert torch.equal(packed_fwd(x, *packed).view(torch.int16), want.view(torch.int16)), (name, M)
+            calls = {"packed": lambda i: packed_fwd(x, *Ps[i]), "unpack": lambda i: packed_fwd(x, *Ps[i], unpack=True),
                      "dense": lambda i: ops.linear_fwd(x, Ws[i])}
             graphs = {k: make_graph(f, pool) for k, f in calls.items()}
             t = {k: [] for k in ("k_packed", "k_dense", "g_packed", "g_unpack", "g_dense")}
@@ -137,7 +145,7 @@ def main():
             print(line, flush=True)
             lines.append(line)
             del graphs
-        del Vs, Ms, Ws
+        del Ps, Ws
         torch.cuda.empty_cache()
     if args.out:
         with open(args.out, "w") as f:

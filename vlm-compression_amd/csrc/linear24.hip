@@ -26,6 +26,11 @@
 //
 // M > vlmc_linear_fwd_24_max_rows() (prefill, the vision tower): compute-bound, so the entry point unpacks into the caller's
 // workspace (unpack24_kernel / unpack48_kernel) and runs the dense launch -- the same bits by construction.
+//
+// The third format is the bitmap format of packbm.hip (ANY mask: values [nnz + 16], meta [N, K / 8], offs [N, ceil(K / 32)],
+// rowptr [N + 1]), entry point vlmc_linear_fwd_bm with a row limit of its own: the same kernel, chain, carry tiles and epilogue; its
+// expansion policy ExpandBM brings its own loads (a chunk is 0 to 8 halfwords at an arbitrary 2-byte offset whose address comes from
+// the metadata, which is therefore fetched one batch further ahead than the values) and its own batch registers.
 #include "common.hpp"
 #include "mfma.hpp"
 
@@ -34,6 +39,12 @@
 #define VLMC_LINEAR24_MAX_ROWS 64
 #endif
 static_assert(VLMC_LINEAR24_MAX_ROWS % 16 == 0 && VLMC_LINEAR24_MAX_ROWS >= 16 && VLMC_LINEAR24_MAX_ROWS <= 64, "16, 32, 48 or 64");
+
+// the bitmap format's own limit, chosen from tools/bench_linear24.py --format bm (profiles/linearbm.md); a multiple of 16 in 16..64
+#ifndef VLMC_LINEARBM_MAX_ROWS
+#define VLMC_LINEARBM_MAX_ROWS 16
+#endif
+static_assert(VLMC_LINEARBM_MAX_ROWS % 16 == 0 && VLMC_LINEARBM_MAX_ROWS >= 16 && VLMC_LINEARBM_MAX_ROWS <= 64, "16, 32, 48 or 64");
 
 namespace vlmc {
 
@@ -47,6 +58,11 @@ struct Linear24Args {
     uint16_t *Y;                  // [M, N], row stride ldy
     int64_t ldx, ldy;
     int M, N, K;
+};
+struct LinearBMArgs : Linear24Args {                                 // values: [nnz + 16]
+    const uint16_t *offs;         // [N, ceil(K / 32)]
+    const int64_t *rowptr;        // [N + 1]
+    int64_t nnz;
 };
 
 // one pack chunk -> the 8 weights of the A fragment.  Per group of four: code = i0 | i1 << 2 (i0 < i1), the two kept values go
@@ -63,46 +79,158 @@ __device__ __forceinline__ u32x4_t expand24(const u32x2_t v, const uint32_t code
     return w;
 }
 
-// The expansion policies: how one pack chunk (8 bytes of values, 1 byte of meta) becomes the 8 weights of the A fragment.
-// `init` runs once per workgroup before the kernel's first barrier.
-struct Expand24 {
-    __device__ __forceinline__ void init(int) {}
-    __device__ __forceinline__ u32x4_t operator()(const u32x2_t v, const uint32_t code) const { return expand24(v, code); }
+// The expansion policies: how the packed bytes of one chunk become the 8 weights of the A fragment.  A policy owns its loads and
+// its batch registers:
+//   Args         the kernel's arguments (Linear24Args, or more)
+//   steps<MT>()  the K-steps of a batch -- what a wave holds in registers at MT tiles of X
+//   Regs<D>      the weight side of a batch
+//   init         once per workgroup, before the kernel's first barrier;   row: this lane's row of W
+//   load         issue the loads of chunk cc into step d and `prime` chunk `ahead`: what must be in flight one batch earlier (the
+//                kernel hands both over clamped: a chunk past K is chunk 0, loaded whatever happens and zeroed when used)
+//   expand       step d -> the fragment;   spare: >= N readable halfwords, loaded in the place of a missing bias
+// The two n:m formats share everything but `expand`: a chunk is 8 bytes of values and 1 byte of meta at an address K alone fixes.
+struct ExpandNM {
+    using Args = Linear24Args;
+    template <int MT> static constexpr int steps() { return MT == 1 ? 8 : (MT == 2 ? 4 : 2); }
+    template <int D> struct Regs {
+        u32x2_t v[D];
+        uint32_t code[D];
+    };
+    const uint16_t *vrow;
+    const uint8_t *mrow;
+    int chunks;
+    static __device__ __forceinline__ const uint16_t *spare(const Args &a) { return a.values; }
+    __device__ __forceinline__ void row(const Args &a, int wrow, int) {
+        chunks = a.K >> 3;
+        vrow = a.values + int64_t(wrow) * (a.K >> 1);
+        mrow = a.meta + int64_t(wrow) * chunks;
+    }
+    template <int D> __device__ __forceinline__ void prime(Regs<D> &, int, int) const {}
+    template <int D> __device__ __forceinline__ void load(Regs<D> &R, int d, int cc, int) const {
+        R.v[d] = *reinterpret_cast<const u32x2_t *>(vrow + cc * 4);
+        R.code[d] = mrow[cc];
+    }
 };
+
+struct Expand24 : ExpandNM {
+    __device__ __forceinline__ void init(int) {}
+    template <int D> __device__ __forceinline__ u32x4_t expand(const Regs<D> &R, int d) const { return expand24(R.v[d], R.code[d]); }
+};
+
+// Selector dword d (positions 2d, 2d + 1) of bitmap byte e for v_perm_b32 over the value halfwords base .. base + 3: bit p of e
+// says that position p holds the next value, value r = popcount of the bits below p.  A position whose value is one of the four
+// gets that halfword's two bytes, every other position 0x0c0c (v_perm_b32's constant 0x00).
+__device__ __forceinline__ uint32_t perm_selector(uint32_t e, uint32_t d, uint32_t base) {
+    uint32_t s = 0x0c0c0c0cu;
+#pragma unroll
+    for (uint32_t h = 0; h < 2; ++h) {
+        const uint32_t p = 2 * d + h, r = uint32_t(__popc(e & ((1u << p) - 1u))) - base;   // position p takes value base + r
+        if (((e >> p) & 1u) && r < 4) s = (s & ~(0xffffu << (16 * h))) | ((2 * r) | (2 * r + 1) << 8) << (16 * h);
+    }
+    return s;
+}
 
 // 4:8: bit j of the byte says that position j holds the next value.  The chunk's 8 bytes are exactly the sources of v_perm_b32
 // ({v[1], v[0]}: selector s picks byte s of the chunk, 0x0c gives 0x00), so each output dword is one perm whose selector comes
 // from a table byte -> four selector dwords (4 KiB of LDS, filled here).  A selector never names anything but a byte of the
 // chunk or zero, and the table is indexed by a byte: whatever the metadata holds, nothing outside the chunk is read.  A byte
 // with more than four bits set places the chunk's four values at its lowest four set bits and zeros at the others.
-struct Expand48 {
+struct Expand48 : ExpandNM {
     const u32x4_t *sel;
     __device__ __forceinline__ void init(int tid) {
         __shared__ u32x4_t table[256];
-        const uint32_t e = uint32_t(tid) >> 2, d = uint32_t(tid) & 3u;         // 64 * L24_WAVES threads = 256 entries x 4 dwords
-        uint32_t s = 0x0c0c0c0cu;
-#pragma unroll
-        for (uint32_t h = 0; h < 2; ++h) {
-            const uint32_t p = 2 * d + h, r = uint32_t(__popc(e & ((1u << p) - 1u)));   // position p takes value r
-            if (((e >> p) & 1u) && r < 4) s = (s & ~(0xffffu << (16 * h))) | ((2 * r) | (2 * r + 1) << 8) << (16 * h);
-        }
-        reinterpret_cast<uint32_t *>(table)[tid] = s;
+        reinterpret_cast<uint32_t *>(table)[tid] = perm_selector(uint32_t(tid) >> 2, uint32_t(tid) & 3u, 0);   // 256 entries x 4 dwords
         sel = table;
     }
-    __device__ __forceinline__ u32x4_t operator()(const u32x2_t v, const uint32_t code) const {
-        const u32x4_t s = sel[code & 0xffu];
+    template <int D> __device__ __forceinline__ u32x4_t expand(const Regs<D> &R, int d) const {
+        const u32x2_t v = R.v[d];
+        const u32x4_t s = sel[R.code[d] & 0xffu];
         u32x4_t w;
 #pragma unroll
-        for (int d = 0; d < 4; ++d) w[d] = __builtin_amdgcn_perm(v[1], v[0], s[d]);
+        for (int j = 0; j < 4; ++j) w[j] = __builtin_amdgcn_perm(v[1], v[0], s[j]);
         return w;
     }
 };
-static_assert(64 * L24_WAVES == 256 * 4, "Expand48::init: one thread per selector dword");
+static_assert(64 * L24_WAVES == 256 * 4, "Expand48 / ExpandBM::init: one thread per selector dword");
 
-// MT tiles of 16 rows of X; D K-steps per batch (what a wave holds in registers); E the format's expansion
+// bm: the byte means what the 4:8 byte means, with 0 to 8 bits set.  The chunk's values are the 0 to 8 halfwords from index
+//     i = min(rowptr[n] + offs[n][s] + popcount(the step's meta bytes before this quarter), nnz)
+// of `values`, fetched as the FIVE ALIGNED dwords from i >> 1 (one 16-byte load that needs 4-byte alignment only, one dword) and
+// shifted down by the odd halfword with v_alignbyte_b32 -- halfwords i & ~1 .. (i & ~1) + 9 <= nnz + 9, inside the 16 of tail
+// whatever the metadata holds.  The step's four meta bytes sit at byte wrow * K / 8 + 4 s of `meta`, at any alignment: the two
+// aligned dwords round it, the second clamped to the last dword that holds a byte of meta (its bytes are then other chunks' or
+// none's: only the bytes of chunks < K / 8 of this row are ever used).
+// Expansion: value r of the chunk is halfword r of the four shifted dwords {v0 .. v3}; output dword j is
+// perm({v1, v0}, A[byte][j]) | perm({v3, v2}, B[byte][j]) with A the selectors of values 0..3 (the 4:8 table) and B those of values
+// 4..7, 0x0c for "not from this pair": 8 KiB of LDS.
+// The address of the values depends on meta and offs, so those are fetched ONE BATCH FURTHER AHEAD (`prime`): when a wave hands on
+// and issues its next batch's value loads, that batch's metadata arrived a whole round ago, and the metadata of the batch after
+// goes out with them.
+typedef uint32_t u32x4_a4_t __attribute__((ext_vector_type(4), aligned(4)));
+struct ExpandBM {
+    using Args = LinearBMArgs;
+    template <int MT> static constexpr int steps() { return MT <= 2 ? 4 : 2; }
+    template <int D> struct Regs {
+        u32x4_t v[D];                          // the aligned dwords 0..3 from i >> 1, v4: the fifth
+        uint32_t v4[D], code[D];               // code: the chunk's byte | (i & 1) << 8
+        uint32_t mlo[D], mhi[D], off[D];       // primed: the two aligned dwords round the step's meta bytes, offs[n][s]
+    };
+    const u32x4_t *sel;                        // [0, 256): A, [256, 512): B
+    const uint32_t *val32, *meta32;
+    const uint16_t *orow;
+    int64_t rp, nnz, mbyte, last_dw;
+    int chunks;
+    uint32_t q8;
+    static __device__ __forceinline__ const uint16_t *spare(const Args &a) { return a.offs; }
+    __device__ __forceinline__ void init(int tid) {
+        __shared__ u32x4_t table[512];
+        reinterpret_cast<uint32_t *>(table)[tid] = perm_selector(uint32_t(tid) >> 2, uint32_t(tid) & 3u, 0);
+        reinterpret_cast<uint32_t *>(table)[1024 + tid] = perm_selector(uint32_t(tid) >> 2, uint32_t(tid) & 3u, 4);
+        sel = table;
+    }
+    __device__ __forceinline__ void row(const Args &a, int wrow, int fq) {
+        chunks = a.K >> 3;
+        val32 = reinterpret_cast<const uint32_t *>(a.values), meta32 = reinterpret_cast<const uint32_t *>(a.meta);
+        orow = a.offs + int64_t(wrow) * ((chunks + 3) >> 2);
+        rp = a.rowptr[wrow], nnz = a.nnz;
+        mbyte = int64_t(wrow) * chunks, last_dw = (int64_t(a.N) * chunks - 1) >> 2;
+        q8 = 8u * uint32_t(fq);
+    }
+    template <int D> __device__ __forceinline__ void prime(Regs<D> &R, int d, int cc) const {
+        const int s = cc >> 2;
+        const int64_t w = (mbyte + 4 * s) >> 2;                       // (chunk 4 s of this row exists: w <= last_dw)
+        R.mlo[d] = meta32[w];
+        R.mhi[d] = meta32[min(w + 1, last_dw)];
+        R.off[d] = orow[s];
+    }
+    template <int D> __device__ __forceinline__ void load(Regs<D> &R, int d, int cc, int ahead) const {
+        const int s = cc >> 2;                                        // (a clamped chunk keeps this lane's quarter: any valid address)
+        const uint32_t m = __builtin_amdgcn_alignbyte(R.mhi[d], R.mlo[d], uint32_t(mbyte + 4 * s) & 3u);
+        const uint32_t before = uint32_t(__popc(m & ((1u << q8) - 1u)));
+        const int64_t i = max(min(rp + int64_t(R.off[d] + before), nnz), int64_t(0));
+        R.code[d] = ((m >> q8) & 0xffu) | uint32_t(i & 1) << 8;
+        const uint32_t *p = val32 + (i >> 1);
+        R.v[d] = *reinterpret_cast<const u32x4_a4_t *>(p);
+        R.v4[d] = p[4];
+        prime(R, d, ahead);
+    }
+    template <int D> __device__ __forceinline__ u32x4_t expand(const Regs<D> &R, int d) const {
+        const uint32_t code = R.code[d], sh = (code >> 8) << 1;       // 0 or 2 bytes
+        const u32x4_t r = R.v[d];
+        const uint32_t v0 = __builtin_amdgcn_alignbyte(r[1], r[0], sh), v1 = __builtin_amdgcn_alignbyte(r[2], r[1], sh),
+                       v2 = __builtin_amdgcn_alignbyte(r[3], r[2], sh), v3 = __builtin_amdgcn_alignbyte(R.v4[d], r[3], sh);
+        const u32x4_t sa = sel[code & 0xffu], sb = sel[256u + (code & 0xffu)];
+        u32x4_t w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = __builtin_amdgcn_perm(v1, v0, sa[j]) | __builtin_amdgcn_perm(v3, v2, sb[j]);
+        return w;
+    }
+};
+
+// MT tiles of 16 rows of X; D K-steps per batch (what a wave holds in registers); E the format's expansion policy
 template <typename T, int MT, typename E>
-__global__ __launch_bounds__(64 * L24_WAVES) void linear24_kernel(const Linear24Args a) {
-    constexpr int D = MT == 1 ? 8 : (MT == 2 ? 4 : 2);
+__global__ __launch_bounds__(64 * L24_WAVES) void linear24_kernel(const typename E::Args a) {
+    constexpr int D = E::template steps<MT>();
     __shared__ f32x4_t carry[MT][64];
     __shared__ int turn;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -115,38 +243,40 @@ __global__ __launch_bounds__(64 * L24_WAVES) void linear24_kernel(const Linear24
     __syncthreads();
 
     // rows past the end are clamped to the last one: their products are never stored
-    const int wrow = min(n0 + fr, a.N - 1);
-    const uint16_t *vrow = a.values + int64_t(wrow) * (a.K >> 1);
-    const uint8_t *mrow = a.meta + int64_t(wrow) * chunks;
+    expand.row(a, min(n0 + fr, a.N - 1), fq);
     const uint16_t *xrow[MT];
 #pragma unroll
     for (int t = 0; t < MT; ++t) xrow[t] = a.X + int64_t(min(t * 16 + fr, a.M - 1)) * a.ldx;
     const int nl = n0 + fq * 4;                            // this lane's four output features
-    // (clamped and never branched round, so that nothing waits for them before the epilogue: without a bias four weights are
-    // loaded in its place and ignored)
-    const uint16_t *bsrc = a.bias != nullptr ? a.bias : a.values;
+    // (clamped and never branched round, so that nothing waits for them before the epilogue: without a bias four halfwords of
+    // the packed weight are loaded in its place and ignored)
+    const uint16_t *bsrc = a.bias != nullptr ? a.bias : E::spare(a);
     uint16_t braw[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) braw[r] = bsrc[min(nl + r, a.N - 1)];
 
     struct Batch {
-        u32x2_t v[D];
-        uint32_t code[D];
+        typename E::template Regs<D> w;
         u32x4_t x[MT][D];
     };
     // every load is issued whatever the chunk: one past K reads chunk 0 and is zeroed when used (no branch round a load)
     auto load = [&](int b, Batch &B) {
+        const int ahead = min(b + L24_WAVES, nb - 1);     // this wave's batch after b: what the policy may have to prime
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-            const int c = (b * D + d) * 4 + fq, cc = c < chunks ? c : 0;
-            B.v[d] = *reinterpret_cast<const u32x2_t *>(vrow + cc * 4);
-            B.code[d] = mrow[cc];
+            const int c = (b * D + d) * 4 + fq, cc = c < chunks ? c : 0, ca = (ahead * D + d) * 4 + fq;
+            expand.load(B.w, d, cc, ca < chunks ? ca : 0);
 #pragma unroll
             for (int t = 0; t < MT; ++t) B.x[t][d] = *reinterpret_cast<const u32x4_t *>(xrow[t] + cc * 8);
         }
     };
 
     Batch cur;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        const int c = (min(wave, nb - 1) * D + d) * 4 + fq;
+        expand.prime(cur.w, d, c < chunks ? c : 0);
+    }
     load(min(wave, nb - 1), cur);
     for (int b = wave; b < nb; b += L24_WAVES) {
         const u32x4_t zero = {0u, 0u, 0u, 0u};
@@ -154,7 +284,7 @@ __global__ __launch_bounds__(64 * L24_WAVES) void linear24_kernel(const Linear24
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             const bool ok = (b * D + d) * 4 + fq < chunks;
-            wf[d] = ok ? expand(cur.v[d], cur.code[d]) : zero;
+            wf[d] = ok ? expand.expand(cur.w, d) : zero;
 #pragma unroll
             for (int t = 0; t < MT; ++t) cur.x[t][d] = ok ? cur.x[t][d] : zero;
         }
@@ -196,7 +326,7 @@ __global__ __launch_bounds__(64 * L24_WAVES) void linear24_kernel(const Linear24
     }
 }
 
-template <typename T, typename E> static void launch_linear24(const Linear24Args &a, hipStream_t s) {
+template <typename T, typename E> static void launch_linear24(const typename E::Args &a, hipStream_t s) {
     const dim3 grid(unsigned((a.N + 15) / 16)), block(64 * L24_WAVES);
     switch ((a.M + 15) / 16) {
         case 1: VLMC_LAUNCH_TIMED((linear24_kernel<T, 1, E>), grid, block, s, a); break;
@@ -220,17 +350,40 @@ extern "C" size_t vlmc_linear_fwd_24_workspace(int64_t M, int64_t N, int64_t K) 
     return linear24_dense_bytes(N, K) + 16;
 }
 
+extern "C" int vlmc_linear_fwd_bm_max_rows(void) { return VLMC_LINEARBM_MAX_ROWS; }
+
+// the same quantity above the bitmap format's own limit
+extern "C" size_t vlmc_linear_fwd_bm_workspace(int64_t M, int64_t N, int64_t K) {
+    if (M <= VLMC_LINEARBM_MAX_ROWS || N <= 0 || K <= 0) return 0;
+    return linear24_dense_bytes(N, K) + 16;
+}
+
+// what every packed entry point asks of the arguments they share; `fn` names the export in every error
+static int linear_packed_check(const char *fn, const void *X, const void *values, const uint8_t *meta, int dtype, int64_t M, int64_t N, int64_t K,
+                               int64_t ldx, const void *Y, int64_t ldy) {
+    VLMC_REQUIRE(dtype == VLMC_F16 || dtype == VLMC_BF16, "%s: dtype must be VLMC_F16 or VLMC_BF16", fn);
+    VLMC_REQUIRE(X && values && meta && Y, "%s: null pointer", fn);
+    VLMC_REQUIRE(M > 0 && N > 0 && K > 0 && M < (int64_t(1) << 31) && N < (int64_t(1) << 31) && K < (int64_t(1) << 31), "%s: bad shape", fn);
+    VLMC_REQUIRE(K % 8 == 0 && ldx % 8 == 0 && ldx >= K && ldy >= N,
+                 "%s: K and the row stride of X must be multiples of 8 elements, ldx >= K, ldy >= N", fn);
+    return VLMC_OK;
+}
+
+template <typename E> static int linear_packed_launch(const char *fn, const typename E::Args &a, int dtype, void *stream) {
+    if (dtype == VLMC_BF16) launch_linear24<bf16_t, E>(a, as_stream(stream));
+    else launch_linear24<f16_t, E>(a, as_stream(stream));
+    VLMC_HIP_CHECK_LAUNCH(fn);
+    return VLMC_OK;
+}
+
 // the one entry point behind both formats: `fn` names the export in every error, `unpack` is the format's unpack export
 template <typename E>
 static int linear_packed_fwd(const char *fn, int (*unpack)(const void *, const uint8_t *, int, int64_t, int64_t, void *, int64_t, uint8_t *, int64_t,
                                                            unsigned int *, void *),
                              const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N, int64_t K,
                              int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream) {
-    VLMC_REQUIRE(dtype == VLMC_F16 || dtype == VLMC_BF16, "%s: dtype must be VLMC_F16 or VLMC_BF16", fn);
-    VLMC_REQUIRE(X && values && meta && Y, "%s: null pointer", fn);
-    VLMC_REQUIRE(M > 0 && N > 0 && K > 0 && M < (int64_t(1) << 31) && N < (int64_t(1) << 31) && K < (int64_t(1) << 31), "%s: bad shape", fn);
-    VLMC_REQUIRE(K % 8 == 0 && ldx % 8 == 0 && ldx >= K && ldy >= N,
-                 "%s: K and the row stride of X must be multiples of 8 elements, ldx >= K, ldy >= N", fn);
+    const int ok = linear_packed_check(fn, X, values, meta, dtype, M, N, K, ldx, Y, ldy);
+    if (ok != VLMC_OK) return ok;
     VLMC_REQUIRE(aligned16(X) && (reinterpret_cast<uintptr_t>(values) & 7u) == 0, "%s: X must be 16-byte, values 8-byte aligned", fn);
     if (M > VLMC_LINEAR24_MAX_ROWS) {
         const size_t dense = linear24_dense_bytes(N, K);
@@ -243,10 +396,7 @@ static int linear_packed_fwd(const char *fn, int (*unpack)(const void *, const u
     }
     const Linear24Args a{static_cast<const uint16_t *>(X), static_cast<const uint16_t *>(values), meta, static_cast<const uint16_t *>(bias),
                          static_cast<uint16_t *>(Y), ldx, ldy, int(M), int(N), int(K)};
-    if (dtype == VLMC_BF16) launch_linear24<bf16_t, E>(a, as_stream(stream));
-    else launch_linear24<f16_t, E>(a, as_stream(stream));
-    VLMC_HIP_CHECK_LAUNCH(fn);
-    return VLMC_OK;
+    return linear_packed_launch<E>(fn, a, dtype, stream);
 }
 
 extern "C" int vlmc_linear_fwd_24(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
@@ -259,4 +409,28 @@ extern "C" int vlmc_linear_fwd_48(const void *X, const void *values, const uint8
                                   int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream) {
     return linear_packed_fwd<Expand48>("vlmc_linear_fwd_48", vlmc_unpack_48, X, values, meta, bias, dtype, M, N, K, ldx, Y, ldy, workspace,
                                        workspace_bytes, stream);
+}
+
+extern "C" int vlmc_linear_fwd_bm(const void *X, const void *values, const uint8_t *meta, const uint16_t *offs, const int64_t *rowptr, int64_t nnz,
+                                  const void *bias, int dtype, int64_t M, int64_t N, int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+    const char *fn = "vlmc_linear_fwd_bm";
+    const int ok = linear_packed_check(fn, X, values, meta, dtype, M, N, K, ldx, Y, ldy);
+    if (ok != VLMC_OK) return ok;
+    VLMC_REQUIRE(offs && rowptr, "%s: null pointer", fn);
+    VLMC_REQUIRE(K <= 65536 && nnz >= 0 && nnz <= N * K, "%s: K must be at most 65536 and 0 <= nnz <= N * K", fn);
+    VLMC_REQUIRE(aligned16(X) && (reinterpret_cast<uintptr_t>(values) & 3u) == 0 && (reinterpret_cast<uintptr_t>(meta) & 3u) == 0,
+                 "%s: X must be 16-byte, values and meta 4-byte aligned", fn);
+    if (M > VLMC_LINEARBM_MAX_ROWS) {
+        const size_t dense = linear24_dense_bytes(N, K);
+        VLMC_REQUIRE(workspace != nullptr && workspace_bytes >= dense + 16 && aligned16(workspace),
+                     "%s: M > %d needs a 16-byte aligned workspace of vlmc_linear_fwd_bm_workspace() bytes", fn, VLMC_LINEARBM_MAX_ROWS);
+        unsigned int *bad = reinterpret_cast<unsigned int *>(static_cast<unsigned char *>(workspace) + dense);
+        const int rc = vlmc_unpack_bm(values, meta, offs, rowptr, nnz, dtype, N, K, workspace, K, nullptr, 0, bad, stream);
+        if (rc != VLMC_OK) return rc;
+        return vlmc_linear_fwd(X, workspace, bias, dtype, M, N, K, ldx, K, Y, ldy, stream);
+    }
+    const LinearBMArgs a{{static_cast<const uint16_t *>(X), static_cast<const uint16_t *>(values), meta, static_cast<const uint16_t *>(bias),
+                          static_cast<uint16_t *>(Y), ldx, ldy, int(M), int(N), int(K)}, offs, rowptr, nnz};
+    return linear_packed_launch<ExpandBM>(fn, a, dtype, stream);
 }

@@ -15,7 +15,9 @@ Packed 2:4 (SURVEY.md §8(f)3 "an optional packed 2:4 format for inference"; the
 `weight_packed24` [out, in / 2] + `weight_meta24` [out, in / 8] (include/vlmc.h: vlmc_pack_24) and back, bit for bit --
 9 / 16 of the bytes of the 16-bit weight, 3 / 8 of weight + mask.  Packed 4:8 (the reference's other n:m regime, prune_n = 4,
 prune_m = 8): `pack_state_dict_48` / `unpack_state_dict_48` / `load_packed_48`, the same functions over `weight_packed48` +
-`weight_meta48` (vlmc_pack_48: one byte per group of eight, bit j = column j kept), the same 9 / 16.
+`weight_meta48` (vlmc_pack_48: one byte per group of eight, bit j = column j kept), the same 9 / 16.  Packed bitmap (ANY mask, what the
+unstructured prunes leave): `pack_state_dict_bm` / `unpack_state_dict_bm` / `load_packed_bm` over `weight_packedbm` + `weight_metabm` +
+`weight_offsbm` + `weight_rowptrbm` (vlmc_pack_bm), (16 d + 1.5) / 16 of the weight's bytes at kept density d.
 """
 from __future__ import annotations
 
@@ -113,57 +115,68 @@ def remaining_proportion(model, orig_total_size) -> float:
 
 PACKED_VALUES, PACKED_META = "weight_packed24", "weight_meta24"
 PACKED_VALUES_48, PACKED_META_48 = "weight_packed48", "weight_meta48"
+PACKED_VALUES_BM, PACKED_META_BM, PACKED_OFFS_BM, PACKED_ROWPTR_BM = "weight_packedbm", "weight_metabm", "weight_offsbm", "weight_rowptrbm"
+_KEYS_24, _KEYS_48 = (PACKED_VALUES, PACKED_META), (PACKED_VALUES_48, PACKED_META_48)
+_KEYS_BM = (PACKED_VALUES_BM, PACKED_META_BM, PACKED_OFFS_BM, PACKED_ROWPTR_BM)
 
 
-def _pack_state_dict(state: dict, keep_masks: bool, group: int, values_key: str, meta_key: str, pack) -> dict:
-    """every (`<name>.weight`, `<name>.mask`) pair whose mask keeps exactly group / 2 of every `group` input columns -> `pack`'s pair"""
+def _keeps_half(group: int):
+    """the n:m formats' rule: the mask keeps exactly group / 2 of every `group` input columns"""
+    return lambda m, shape: bool((m.reshape(shape[0], -1, group).sum(-1) == group // 2).all())
+
+
+def _pack_state_dict(state: dict, keep_masks: bool, accepts, keys: tuple, pack) -> dict:
+    """every (`<name>.weight`, `<name>.mask`) pair whose bool mask the format `accepts(mask, shape)` -> `pack`'s tensors under `keys`"""
     out = {}
     for k, v in state.items():
         if k.endswith(".weight") and k[:-6] + "mask" in state and isinstance(v, torch.Tensor) and v.is_cuda and v.dim() == 2 and \
                 v.dtype in (torch.float16, torch.bfloat16) and v.shape[1] % 8 == 0:
             m = state[k[:-6] + "mask"]
-            if m.shape == v.shape and m.dtype == torch.bool and bool((m.reshape(v.shape[0], -1, group).sum(-1) == group // 2).all()):
+            if m.shape == v.shape and m.dtype == torch.bool and accepts(m, v.shape):
                 w = v if v.stride(1) == 1 else v.contiguous()
                 # (what is stored is W . mask: under SparseLoRA the pruned positions of `weight` are zero already, lora.py:362)
-                values, meta = pack(w, m if m.stride(1) == 1 else m.contiguous())
-                out[k[:-6] + values_key], out[k[:-6] + meta_key] = values, meta
+                for key, t in zip(keys, pack(w, m if m.stride(1) == 1 else m.contiguous())):
+                    out[k[:-6] + key] = t
                 continue
         out[k] = v
     if not keep_masks:
-        for k in [k for k in out if k.endswith(".mask") and k[:-4] + values_key in out]:
+        for k in [k for k in out if k.endswith(".mask") and k[:-4] + keys[0] in out]:
             del out[k]
     return out
 
 
-def _unpack_state_dict(state: dict, device, values_key: str, meta_key: str, unpack) -> dict:
+def _unpack_state_dict(state: dict, device, keys: tuple, unpack) -> dict:
     out = {}
     for k, v in state.items():
-        if k.endswith("." + values_key):
-            base = k[:-len(values_key)]
-            values, meta = v, state[base + meta_key]
+        if k.endswith("." + keys[0]):
+            base = k[:-len(keys[0])]
+            packed = [state[base + key] for key in keys]
             if device is not None:
-                values, meta = values.to(device), meta.to(device)
-            w, m = unpack(values.contiguous(), meta.contiguous())
+                packed = [t.to(device) for t in packed]
+            w, m = unpack(*(t.contiguous() for t in packed))
             out[base + "weight"], out[base + "mask"] = w, m
-        elif not k.endswith("." + meta_key):
+        elif not any(k.endswith("." + key) for key in keys[1:]):
             out.setdefault(k, v)
     return out
 
 
-def _load_packed(model, packed_state: dict, strict: bool, tag: str, values_key: str, meta_key: str, is_valid, cls):
-    """swap a `cls` in for every module whose `<name>.<values_key>` is in `packed_state` (metadata validated once), then load"""
+def _load_packed(model, packed_state: dict, strict: bool, tag: str, keys: tuple, is_valid, cls, checked: tuple = None):
+    """swap a `cls` in for every module whose `<name>.<keys[0]>` is in `packed_state` (metadata validated once: `is_valid` takes the
+    tensors of keys[1:], then the values; `checked`: the keys a failure is blamed on, keys[1] by default), then load"""
     state, fn = dict(packed_state), "load_packed_" + tag
-    for k in [k for k in state if k.endswith("." + values_key)]:
-        name = k[:-len(values_key) - 1]
-        values, meta = state[k], state.get(name + "." + meta_key)
-        if meta is None:
-            raise KeyError(f"{fn}: {name}.{meta_key} is missing")
-        if not is_valid(meta):
-            raise ValueError(f"{fn}: {name}.{meta_key} holds codes that pack_{tag} never writes")
+    for k in [k for k in state if k.endswith("." + keys[0])]:
+        name = k[:-len(keys[0]) - 1]
+        packed = [state.get(name + "." + key) for key in keys]
+        for key, t in zip(keys, packed):
+            if t is None:
+                raise KeyError(f"{fn}: {name}.{key} is missing")
+        if not is_valid(*packed[1:], packed[0]):
+            blamed = " / ".join(f"{name}.{key}" for key in (checked or keys[1:2]))
+            raise ValueError(f"{fn}: {blamed} {'hold entries' if checked else 'holds codes'} that pack_{tag} never writes")
         old = model.get_submodule(name)
-        dev = next((t.device for t in list(old.parameters(recurse=False)) + list(old.buffers(recurse=False))), values.device)
+        dev = next((t.device for t in list(old.parameters(recurse=False)) + list(old.buffers(recurse=False))), packed[0].device)
         bias = state.get(name + ".bias")
-        new = cls(torch.empty_like(values, device=dev), torch.empty_like(meta, device=dev), None if bias is None else torch.empty_like(bias, device=dev))
+        new = cls(*(torch.empty_like(t, device=dev) for t in packed), bias=None if bias is None else torch.empty_like(bias, device=dev))
         new.train(old.training)
         parent, _, child = name.rpartition(".")
         setattr(model.get_submodule(parent) if parent else model, child, new)
@@ -177,13 +190,13 @@ def pack_state_dict_24(state: dict, keep_masks: bool = False) -> dict:
     Pairs that are not 2:4 (unstructured masks, 4:8 masks, fp32 weights, widths that are not multiples of 8) stay as they are.
     `keep_masks`: keep the `mask` entries of packed linears too (they are recoverable from the metadata)."""
     from . import ops
-    return _pack_state_dict(state, keep_masks, 4, PACKED_VALUES, PACKED_META, ops.pack_24)
+    return _pack_state_dict(state, keep_masks, _keeps_half(4), _KEYS_24, ops.pack_24)
 
 
 def unpack_state_dict_24(state: dict, device=None) -> dict:
     """The dense state dict back: `<name>.weight` (zeros where nothing was kept) and `<name>.mask` for every packed pair."""
     from . import ops
-    return _unpack_state_dict(state, device, PACKED_VALUES, PACKED_META, ops.unpack_24)
+    return _unpack_state_dict(state, device, _KEYS_24, ops.unpack_24)
 
 
 def load_packed_24(model, packed_state: dict, strict: bool = True):
@@ -193,7 +206,7 @@ def load_packed_24(model, packed_state: dict, strict: bool = True):
     recoverable from the metadata and dropped.  Afterwards `model.state_dict()` is the packed state: it goes through
     `unpack_state_dict_24` / `pack_state_dict_24` bit for bit.  Returns `load_state_dict`'s result."""
     from . import packed24
-    return _load_packed(model, packed_state, strict, "24", PACKED_VALUES, PACKED_META, packed24.meta_24_is_valid, packed24.Linear24)
+    return _load_packed(model, packed_state, strict, "24", _KEYS_24, lambda meta, _values: packed24.meta_24_is_valid(meta), packed24.Linear24)
 
 
 def pack_state_dict_48(state: dict, keep_masks: bool = False) -> dict:
@@ -202,17 +215,44 @@ def pack_state_dict_48(state: dict, keep_masks: bool = False) -> dict:
     weight's bytes; every other pair stays as it is.  A 2:4 mask is also a 4:8 mask and is packed here: run `pack_state_dict_24`
     first on a state dict whose 2:4 linears should get the 2:4 selector form."""
     from . import ops
-    return _pack_state_dict(state, keep_masks, 8, PACKED_VALUES_48, PACKED_META_48, ops.pack_48)
+    return _pack_state_dict(state, keep_masks, _keeps_half(8), _KEYS_48, ops.pack_48)
 
 
 def unpack_state_dict_48(state: dict, device=None) -> dict:
     """The dense state dict back: `<name>.weight` (zeros where nothing was kept) and `<name>.mask` for every packed 4:8 pair."""
     from . import ops
-    return _unpack_state_dict(state, device, PACKED_VALUES_48, PACKED_META_48, ops.unpack_48)
+    return _unpack_state_dict(state, device, _KEYS_48, ops.unpack_48)
 
 
 def load_packed_48(model, packed_state: dict, strict: bool = True):
     """`load_packed_24` for what `pack_state_dict_48` made: the modules whose `<name>.weight_packed48` key is in `packed_state`
     become `packed48.Linear48`, each `weight_meta48` validated once here (every byte has popcount 4; the kernels trust it)."""
     from . import packed48
-    return _load_packed(model, packed_state, strict, "48", PACKED_VALUES_48, PACKED_META_48, packed48.meta_48_is_valid, packed48.Linear48)
+    return _load_packed(model, packed_state, strict, "48", _KEYS_48, lambda meta, _values: packed48.meta_48_is_valid(meta), packed48.Linear48)
+
+
+def pack_state_dict_bm(state: dict, keep_masks: bool = False) -> dict:
+    """`pack_state_dict_24` for ANY mask: every (`<name>.weight`, `<name>.mask`) pair of a 16-bit weight (in % 8 == 0, in <= 65536)
+    whose packed bytes are fewer than its dense ones becomes `<name>.weight_packedbm` / `weight_metabm` / `weight_offsbm` /
+    `weight_rowptrbm` (include/vlmc.h: vlmc_pack_bm), (16 d + 1.5) / 16 of the weight's bytes at kept density d; every other pair stays
+    as it is.  n:m masks are masks and are packed here too: run `pack_state_dict_24` / `pack_state_dict_48` FIRST on a state dict whose
+    n:m linears should get the tighter 9 / 16 forms."""
+    from . import ops, packedbm
+    return _pack_state_dict(state, keep_masks, packedbm.is_mask_bm, _KEYS_BM, ops.pack_bm)
+
+
+def unpack_state_dict_bm(state: dict, device=None) -> dict:
+    """The dense state dict back: `<name>.weight` (zeros where nothing was kept) and `<name>.mask` for every bitmap-packed linear."""
+    from . import ops
+    return _unpack_state_dict(state, device, _KEYS_BM, ops.unpack_bm)
+
+
+def load_packed_bm(model, packed_state: dict, strict: bool = True):
+    """`load_packed_24` for what `pack_state_dict_bm` made: the modules whose `<name>.weight_packedbm` key is in `packed_state` become
+    `packedbm.LinearBM`; `weight_offsbm` and `weight_rowptrbm` are validated once here against the bitmap's running popcount
+    (`packedbm.meta_bm_is_valid`; the kernels trust them)."""
+    from . import packedbm
+    return _load_packed(model, packed_state, strict, "bm", _KEYS_BM,
+                        lambda meta, offs, rowptr, values: values.dim() == 1 and values.numel() >= 16 and
+                        packedbm.meta_bm_is_valid(meta, offs, rowptr, values.numel() - 16), packedbm.LinearBM,
+                        checked=(PACKED_OFFS_BM, PACKED_ROWPTR_BM))

@@ -689,7 +689,7 @@ def unpack_48(values: torch.Tensor, meta: torch.Tensor, want_mask: bool = True):
     return _unpack_nm(_FMT48, values, meta, want_mask)
 
 
-_linear24_ws = Workspace()        # the dense weight of the unpack route: grows to the largest one seen, shared by every layer and both formats
+_linear24_ws = Workspace()        # the dense weight of the unpack route: grows to the largest one seen, shared by every layer and every format
 
 
 def linear_fwd_24_max_rows() -> int:
@@ -714,29 +714,34 @@ def linear_fwd_48_supported(x: torch.Tensor, values: torch.Tensor, meta: torch.T
     return linear_fwd_24_supported(x, values, meta, bias)
 
 
+def _linear_fwd_packed(tag, x, N, K, bias, unpack, packed, workspace):
+    """The forward every packed format shares: `packed` is what the format's exports take between X and the bias (`vlmc_linear_fwd_<tag>`)
+    and before the dtype (`vlmc_unpack_<tag>`), `workspace` the export that sizes the scratch weight above the format's row limit."""
+    x2, M, ld = _rows(x, K, aligned=True)
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    if M == 0:
+        return y.reshape(*x.shape[:-1], N)
+    lib, dt, bptr = _lib.load(), _DT[x.dtype], bias.data_ptr() if bias is not None else None
+    if unpack:
+        dense = (N * K * 2 + 15) // 16 * 16
+        ws = _linear24_ws.get(dense + 16, x.device)        # (the last 16 bytes: the unpack kernel's bad-group counter, unused)
+        _lib.check(getattr(lib, "vlmc_unpack_" + tag)(*packed, dt, N, K, ws.data_ptr(), K, None, 0, ws.data_ptr() + dense, _stream()))
+        _lib.check(lib.vlmc_linear_fwd(x2.data_ptr(), ws.data_ptr(), bptr, dt, M, N, K, ld, K, y.data_ptr(), N, _stream()))
+        return y.reshape(*x.shape[:-1], N)
+    nbytes = int(getattr(lib, workspace)(M, N, K))
+    ws = _linear24_ws.get(nbytes, x.device) if nbytes else None
+    _lib.check(getattr(lib, "vlmc_linear_fwd_" + tag)(x2.data_ptr(), *packed, bptr, dt, M, N, K, ld, y.data_ptr(), N,
+                                                      ws.data_ptr() if ws is not None else None, nbytes, _stream()))
+    return y.reshape(*x.shape[:-1], N)
+
+
 def _linear_fwd_nm(f, x, values, meta, bias, unpack):
     _need_gpu(x, values, meta, bias)
     if not linear_fwd_24_supported(x, values, meta, bias):
         raise TypeError(f"vlmc.linear_fwd_{f['tag']}: fp16/bf16 x [.., K], contiguous values [N, K / 2] of the same dtype, meta [N, K / 8] uint8 "
                         "(K % 8 == 0) and a contiguous bias [N] of that dtype expected")
-    N, K = values.shape[0], 2 * values.shape[1]
-    x2, M, ld = _rows(x, K, aligned=True)
-    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    if M == 0:
-        return y.reshape(*x.shape[:-1], N)
-    lib, dt, bptr = _lib.load(), _DT[values.dtype], bias.data_ptr() if bias is not None else None
-    if unpack:
-        dense = (N * K * 2 + 15) // 16 * 16
-        ws = _linear24_ws.get(dense + 16, x.device)        # (the last 16 bytes: the unpack kernel's bad-group counter, unused)
-        _lib.check(getattr(lib, "vlmc_unpack_" + f["tag"])(values.data_ptr(), meta.data_ptr(), dt, N, K, ws.data_ptr(), K, None, 0,
-                                                           ws.data_ptr() + dense, _stream()))
-        _lib.check(lib.vlmc_linear_fwd(x2.data_ptr(), ws.data_ptr(), bptr, dt, M, N, K, ld, K, y.data_ptr(), N, _stream()))
-        return y.reshape(*x.shape[:-1], N)
-    nbytes = int(lib.vlmc_linear_fwd_24_workspace(M, N, K))
-    ws = _linear24_ws.get(nbytes, x.device) if nbytes else None
-    _lib.check(getattr(lib, "vlmc_linear_fwd_" + f["tag"])(x2.data_ptr(), values.data_ptr(), meta.data_ptr(), bptr, dt, M, N, K, ld, y.data_ptr(), N,
-                                                           ws.data_ptr() if ws is not None else None, nbytes, _stream()))
-    return y.reshape(*x.shape[:-1], N)
+    return _linear_fwd_packed(f["tag"], x, values.shape[0], 2 * values.shape[1], bias, unpack, (values.data_ptr(), meta.data_ptr()),
+                              "vlmc_linear_fwd_24_workspace")
 
 
 def linear_fwd_24(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None,
@@ -756,6 +761,84 @@ def linear_fwd_48(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bia
     (`linear_fwd_24_max_rows()`) and scratch weight.  `meta` is trusted (`pack_48` wrote it, or `formats.load_packed_48`
     validated it).  `unpack`: the unpack route whatever the number of rows (the cross-check of the packed kernel)."""
     return _linear_fwd_nm(_FMT48, x, values, meta, bias, unpack)
+
+
+# ---- the bitmap format (csrc/packbm.hip): any mask ------------------------------------------------------------------------------
+def _bm_shapes_ok(values, meta, offs, rowptr) -> bool:
+    return (values.dim() == 1 and values.dtype in _16BIT and values.numel() >= 16 and meta.dim() == 2 and meta.dtype == torch.uint8
+            and 0 < meta.shape[1] <= 8192 and offs.dtype == torch.uint16 and offs.shape == (meta.shape[0], (meta.shape[1] + 3) // 4)
+            and rowptr.dtype == torch.int64 and rowptr.shape == (meta.shape[0] + 1,)
+            and values.is_contiguous() and meta.is_contiguous() and offs.is_contiguous() and rowptr.is_contiguous())
+
+
+def pack_bm(weight: torch.Tensor, mask: torch.Tensor):
+    """(values [nnz + 16], meta [out, in / 8] uint8, offs [out, ceil(in / 32)] uint16, rowptr [out + 1] int64) of a 16-bit weight under
+    ANY bool mask (1 = keep): the bitmap format of include/vlmc.h (vlmc_pack_bm_rows, vlmc_pack_bm).  in % 8 == 0, in <= 65536.  One
+    host read (rowptr[out], to size `values`)."""
+    _need_gpu(weight, mask)
+    if weight.dim() != 2 or weight.dtype not in _16BIT or mask.shape != weight.shape or mask.dtype not in (torch.bool, torch.uint8) or \
+            weight.shape[1] % 8 or not 0 < weight.shape[1] <= 65536 or weight.shape[0] == 0 or weight.stride(1) != 1 or mask.stride(1) != 1:
+        raise TypeError("vlmc.pack_bm: a 16-bit weight [out, in] (in % 8 == 0, in <= 65536) and a bool mask of the same shape, rows contiguous, expected")
+    out_f, in_f = weight.shape
+    lib, dev = _lib.load(), weight.device
+    rowptr = torch.empty(out_f + 1, dtype=torch.int64, device=dev)
+    _lib.check(lib.vlmc_pack_bm_rows(mask.data_ptr(), mask.stride(0), out_f, in_f, rowptr.data_ptr(), _stream()))
+    nnz = int(rowptr[-1].item())
+    values = torch.empty(nnz + 16, dtype=weight.dtype, device=dev)
+    meta = torch.empty((out_f, in_f // 8), dtype=torch.uint8, device=dev)
+    offs = torch.empty((out_f, (in_f + 31) // 32), dtype=torch.uint16, device=dev)
+    _lib.check(lib.vlmc_pack_bm(weight.data_ptr(), _DT[weight.dtype], out_f, in_f, weight.stride(0), mask.data_ptr(), mask.stride(0),
+                                rowptr.data_ptr(), nnz, values.data_ptr(), meta.data_ptr(), offs.data_ptr(), _stream()))
+    return values, meta, offs, rowptr
+
+
+def unpack_bm(values: torch.Tensor, meta: torch.Tensor, offs: torch.Tensor, rowptr: torch.Tensor, want_mask: bool = True):
+    """The dense [out, in] weight (zeros where nothing was kept) and the bool mask of `pack_bm`'s output (vlmc_unpack_bm).  Raises
+    ValueError when `offs` or `rowptr` disagree with the bitmap; nothing outside `values` is read even then."""
+    _need_gpu(values, meta, offs, rowptr)
+    if not _bm_shapes_ok(values, meta, offs, rowptr):
+        raise TypeError("vlmc.unpack_bm: contiguous values [nnz + 16] (16-bit), meta [out, in / 8] (uint8), offs [out, ceil(in / 32)] (uint16) and "
+                        "rowptr [out + 1] (int64) expected")
+    out_f, in_f = meta.shape[0], 8 * meta.shape[1]
+    w = torch.empty((out_f, in_f), dtype=values.dtype, device=values.device)
+    mask = torch.empty((out_f, in_f), dtype=torch.bool, device=values.device) if want_mask else None
+    bad = torch.zeros(1, dtype=torch.int32, device=values.device)
+    _lib.check(_lib.load().vlmc_unpack_bm(values.data_ptr(), meta.data_ptr(), offs.data_ptr(), rowptr.data_ptr(), values.numel() - 16,
+                                          _DT[values.dtype], out_f, in_f, w.data_ptr(), in_f, None if mask is None else mask.data_ptr(), in_f,
+                                          bad.data_ptr(), _stream()))
+    if int(bad.item()):
+        raise ValueError("vlmc.unpack_bm: offs / rowptr hold entries that pack_bm never writes for this bitmap")
+    return w, mask
+
+
+def linear_fwd_bm_max_rows() -> int:
+    """Most rows of x the bitmap format's packed kernel itself takes (vlmc_linear_fwd_bm_max_rows: its own limit, not the n:m one);
+    above, `linear_fwd_bm` unpacks into scratch."""
+    return int(_lib.load().vlmc_linear_fwd_bm_max_rows())
+
+
+def linear_fwd_bm_supported(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, offs: torch.Tensor, rowptr: torch.Tensor,
+                            bias: torch.Tensor | None = None) -> bool:
+    """Whether `linear_fwd_bm` takes this call: 16-bit x [.., K] and values [nnz + 16] of one dtype, meta [N, K / 8] uint8, offs
+    [N, ceil(K / 32)] uint16, rowptr [N + 1] int64, all contiguous and on the GPU, values and meta 4-byte aligned."""
+    return (all(t.is_cuda for t in (x, values, meta, offs, rowptr)) and _bm_shapes_ok(values, meta, offs, rowptr) and x.dtype == values.dtype
+            and x.dim() >= 1 and x.shape[-1] == 8 * meta.shape[1] and values.data_ptr() % 4 == 0 and meta.data_ptr() % 4 == 0
+            and (bias is None or (bias.is_cuda and bias.dtype == values.dtype and bias.is_contiguous() and bias.shape == (meta.shape[0],))))
+
+
+def linear_fwd_bm(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, offs: torch.Tensor, rowptr: torch.Tensor,
+                  bias: torch.Tensor | None = None, unpack: bool = False) -> torch.Tensor:
+    """y = x @ unpack_bm(values, meta, offs, rowptr).T + bias computed FROM the bitmap-packed weight (vlmc_linear_fwd_bm): bit for bit
+    `linear_fwd(x, unpack_bm(..)[0], bias)`, any leading dims.  Up to `linear_fwd_bm_max_rows()` rows one kernel reads the packed bytes
+    and expands them in registers; more rows unpack into the per-device scratch weight the n:m formats use and run the dense kernel.
+    The metadata is trusted (`pack_bm` wrote it, or `formats.load_packed_bm` validated it).  `unpack`: the unpack route whatever the
+    number of rows (the cross-check of the packed kernel)."""
+    _need_gpu(x, values, meta, offs, rowptr, bias)
+    if not linear_fwd_bm_supported(x, values, meta, offs, rowptr, bias):
+        raise TypeError("vlmc.linear_fwd_bm: fp16/bf16 x [.., K], contiguous values [nnz + 16] of the same dtype, meta [N, K / 8] uint8, offs "
+                        "[N, ceil(K / 32)] uint16, rowptr [N + 1] int64 (K % 8 == 0, K <= 65536) and a contiguous bias [N] of that dtype expected")
+    packed = (values.data_ptr(), meta.data_ptr(), offs.data_ptr(), rowptr.data_ptr(), values.numel() - 16)
+    return _linear_fwd_packed("bm", x, meta.shape[0], 8 * meta.shape[1], bias, unpack, packed, "vlmc_linear_fwd_bm_workspace")
 
 
 def hessian_accum(H: torch.Tensor, x: torch.Tensor, alpha: float, beta: float, rows=None) -> torch.Tensor:

@@ -50,20 +50,32 @@ def is_mask_24(mask, shape) -> bool:
 
 
 class _PackedLinear(nn.Module):
-    """What `Linear24` and `packed48.Linear48` share: everything but the buffer names and the three ops of the format."""
-    _VALUES = _META = _TAG = None                        # the state-dict names of the two buffers; "24" / "48": ops.pack_<tag>, ..
+    """What `Linear24`, `packed48.Linear48` and `packedbm.LinearBM` share: everything but the constructor's signature, the buffer names,
+    their shapes and the three ops of the format.  A subclass spells its own `__init__(self, <its buffers>, bias=None)` and hands the
+    buffers on as one tuple; `cls(*packed, bias=bias)` therefore builds any of them."""
+    _NAMES = ()                                          # the state-dict names of the packed buffers, in the order ops.pack_<tag> returns them
+    _TAG = None                                          # "24" / "48" / "bm": ops.pack_<tag>, ops.unpack_<tag>, ops.linear_fwd_<tag>
+    _LAYOUT = "values [out, in / 2] (fp16 / bf16) and meta [out, in / 8] (uint8)"
 
-    def __init__(self, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None):
-        super().__init__()
-        cls = type(self).__name__
+    @staticmethod
+    def _features(values, meta):
+        """(out_features, in_features) of well-formed packed buffers, None otherwise (the two n:m formats' rule)"""
         if values.dim() != 2 or values.dtype not in _16BIT or meta.dtype != torch.uint8 or values.shape[1] % 4 or \
                 tuple(meta.shape) != (values.shape[0], values.shape[1] // 4):
-            raise TypeError(f"{cls}: values [out, in / 2] (fp16 / bf16) and meta [out, in / 8] (uint8) expected")
-        if bias is not None and (bias.dtype != values.dtype or tuple(bias.shape) != (values.shape[0],)):
+            return None
+        return values.shape[0], 2 * values.shape[1]
+
+    def __init__(self, packed: tuple, bias: torch.Tensor | None):
+        super().__init__()
+        cls = type(self).__name__
+        feats = self._features(*packed)
+        if feats is None:
+            raise TypeError(f"{cls}: {self._LAYOUT} expected")
+        if bias is not None and (bias.dtype != packed[0].dtype or tuple(bias.shape) != (feats[0],)):
             raise TypeError(f"{cls}: a bias [out] of the values' dtype expected")
-        self.out_features, self.in_features = values.shape[0], 2 * values.shape[1]
-        self.register_buffer(self._VALUES, values.detach().contiguous())
-        self.register_buffer(self._META, meta.contiguous())
+        self.out_features, self.in_features = feats
+        for name, t in zip(self._NAMES, packed):
+            self.register_buffer(name, t.detach().contiguous())
         self.register_buffer("bias", None if bias is None else bias.detach().contiguous())
 
     @classmethod
@@ -71,9 +83,12 @@ class _PackedLinear(nn.Module):
         from . import ops
         return getattr(ops, f"{name}_{cls._TAG}")
 
+    def _packed(self) -> tuple:
+        return tuple(getattr(self, name) for name in self._NAMES)
+
     @property
     def dtype(self):
-        return getattr(self, self._VALUES).dtype
+        return getattr(self, self._NAMES[0]).dtype
 
     def extra_repr(self):
         return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, dtype={self.dtype}"
@@ -86,19 +101,19 @@ class _PackedLinear(nn.Module):
             raise RuntimeError(f"{cls} is inference only: its input requires a gradient")
         if x.dtype != self.dtype:
             raise TypeError(f"{cls}: input of dtype {x.dtype}, weights packed as {self.dtype}")
-        return self._op("linear_fwd")(x, getattr(self, self._VALUES), getattr(self, self._META), self.bias)
+        return self._op("linear_fwd")(x, *self._packed(), self.bias)
 
     @classmethod
     def from_linear(cls, module: nn.Module, mask: torch.Tensor | None = None):
         """Pack `module.weight . mask` (`mask`: the module's own `mask` by default) on the GPU."""
         mask = module.mask if mask is None else mask
         w = module.weight.detach()
-        values, meta = cls._op("pack")(w if w.stride(1) == 1 else w.contiguous(), mask if mask.stride(1) == 1 else mask.contiguous())
-        return cls(values, meta, None if module.bias is None else module.bias.detach())
+        packed = cls._op("pack")(w if w.stride(1) == 1 else w.contiguous(), mask if mask.stride(1) == 1 else mask.contiguous())
+        return cls(*packed, bias=None if module.bias is None else module.bias.detach())
 
     def to_linear(self) -> nn.Linear:
         """The dense `nn.Linear` back: weight W . mask, the `mask` attribute a prune leaves (wanda_pruner.py:339)."""
-        w, mask = self._op("unpack")(getattr(self, self._VALUES), getattr(self, self._META))
+        w, mask = self._op("unpack")(*self._packed())
         lin = nn.Linear(self.in_features, self.out_features, bias=self.bias is not None, device="meta")
         lin.weight = nn.Parameter(w, requires_grad=False)
         if self.bias is not None:
@@ -107,11 +122,18 @@ class _PackedLinear(nn.Module):
         return lin.train(self.training)
 
 
-class Linear24(_PackedLinear):
+class _PackedLinearNM(_PackedLinear):
+    """the two n:m formats' constructor: two buffers"""
+
+    def __init__(self, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None):
+        super().__init__((values, meta), bias)
+
+
+class Linear24(_PackedLinearNM):
     """A linear whose weight exists only as `weight_packed24` [out, in / 2] + `weight_meta24` [out, in / 8] (buffers, the names of
     `formats.pack_state_dict_24`) and a `bias` buffer.  `forward(x, dense=False)` takes the reference model files' call
     `lin(x, dense)` (eva_vit.py:54-60)."""
-    _VALUES, _META, _TAG = PACKED_VALUES, PACKED_META, "24"
+    _NAMES, _TAG = (PACKED_VALUES, PACKED_META), "24"
 
 
 def _empty_adapter(m) -> bool:
@@ -120,7 +142,7 @@ def _empty_adapter(m) -> bool:
 
 
 def _packable(m, from_zeros: bool, is_mask=None, mask_from_zeros=None):
-    """The n:m mask under which module `m` can be replaced, or None (`is_mask`, `mask_from_zeros`: the format's; 2:4 by default)."""
+    """The mask under which module `m` can be replaced, or None (`is_mask`, `mask_from_zeros`: the format's; 2:4 by default)."""
     from lavis.peft.src.peft.tuners.lora import Linear as LoraLinear
     is_mask, mask_from_zeros = is_mask or is_mask_24, mask_from_zeros or mask_24_from_zeros
     if type(m) is nn.Linear:
@@ -138,9 +160,10 @@ def _packable(m, from_zeros: bool, is_mask=None, mask_from_zeros=None):
         return mask if is_mask(mask, w.shape) else None
     if from_zeros and type(m) is nn.Linear:
         try:
-            return mask_from_zeros(w.detach())
+            mask = mask_from_zeros(w.detach())
         except ValueError:
             return None
+        return mask if is_mask(mask, w.shape) else None
     return None
 
 

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from .formats import PACKED_META_48, PACKED_VALUES_48
-from .packed24 import _mask_nm_from_zeros, _pack_model_, _PackedLinear, _unpack_model_
+from .packed24 import _mask_nm_from_zeros, _pack_model_, _PackedLinearNM, _unpack_model_
 
 
 def meta_48_is_valid(meta: torch.Tensor) -> bool:
@@ -40,11 +40,11 @@ def is_mask_48(mask, shape) -> bool:
             and shape[1] % 8 == 0 and bool((mask.reshape(shape[0], -1, 8).sum(-1) == 4).all()))
 
 
-class Linear48(_PackedLinear):
+class Linear48(_PackedLinearNM):
     """A linear whose weight exists only as `weight_packed48` [out, in / 2] + `weight_meta48` [out, in / 8] (buffers, the names of
     `formats.pack_state_dict_48`) and a `bias` buffer.  `forward(x, dense=False)` takes the reference model files' call
     `lin(x, dense)` (eva_vit.py:54-60) and refuses what `Linear24` refuses."""
-    _VALUES, _META, _TAG = PACKED_VALUES_48, PACKED_META_48, "48"
+    _NAMES, _TAG = (PACKED_VALUES_48, PACKED_META_48), "48"
 
 
 def pack_model_48_(model: nn.Module, from_zeros: bool = False) -> list:
