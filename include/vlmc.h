@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VLMC_ABI_VERSION 26
+#define VLMC_ABI_VERSION 27
 
 #define VLMC_OK 0
 #define VLMC_EINVAL (-1)     /* bad argument (shape, dtype, alignment, null pointer) */
@@ -270,6 +270,22 @@ int vlmc_linear_fwd_24(const void *X, const void *values, const uint8_t *meta, c
  * vlmc_linear_fwd_24_workspace() answer for this entry point too.                                                             */
 int vlmc_linear_fwd_48(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
                        int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream);
+/* The two linears above at ANY M >= 1 with NO workspace (prefill, the vision tower: the dense zero-filled forward of a model pruned
+ * 2:4 or 4:8, train.py:626-637, :677-714, computed from the packed bytes): the tiled GEMM behind vlmc_linear_fwd with its weight
+ * operand packed -- a workgroup's threads load 8 bytes of values and 1 byte of meta per 8 input columns and expand them on the way
+ * into LDS, so the weight is read once at 9 / 16 of its dense bytes and no dense copy exists anywhere.  Bit for bit vlmc_linear_fwd
+ * on vlmc_unpack_24 / vlmc_unpack_48 of the same buffers, in every tile shape (the shape is picked as vlmc_linear_fwd picks it).
+ * Arguments as vlmc_linear_fwd_24 without the workspace: K and ldx multiples of 8, ldx >= K, ldy >= N, X 16-byte and values 8-byte
+ * aligned, dtype VLMC_F16 or VLMC_BF16 (VLMC_F32: VLMC_EINVAL), bias [N] in the dtype or NULL; every refusal happens before the
+ * device is touched.  meta is TRUSTED as above: whatever a byte holds, nothing outside its own chunk is read.
+ * vlmc_linear_fwd_24_tiled_max_rows(): the largest M for which this kernel measured faster than unpacking into a workspace (both
+ * formats; a build-time constant chosen from tools/bench_linear24.py --tiled; 0 = at no M, else >= vlmc_linear_fwd_24_max_rows()):
+ * advice for callers that route by M, as vlmc.ops does -- the entry points themselves take any M.                                */
+int vlmc_linear_fwd_24_tiled_max_rows(void);
+int vlmc_linear_fwd_24_tiled(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
+                             int64_t K, int64_t ldx, void *Y, int64_t ldy, void *stream);
+int vlmc_linear_fwd_48_tiled(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
+                             int64_t K, int64_t ldx, void *Y, int64_t ldy, void *stream);
 
 /* ---- packed UNSTRUCTURED weights, "bm" (any mask: what the unstructured branch of every pruner leaves, wanda_pruner.py:330-337, and
  * the `mask` a prune puts on a module, :339; the reference has no packed format) -------------------------------------------------

@@ -12,6 +12,14 @@ Two clocks, both on the device:
 Every row is measured `--repeats` times with the routes alternating; the table prints the median and the spread (max - min).
 
     python tools/bench_linear24.py [--format 24|48|bm] [--density 0.5] [--only v7b] [--rows 1,8,16] [--repeats 3] [--out profiles/linear24.md]
+
+`--tiled` (formats 24 and 48): the PREFILL sizes instead -- for every shape above plus the four ViT-g linears and every row count of the
+ladder 65 .. 4096, on the graph clock, alternating: (a) the unpack route (unpack into scratch + dense kernel: what runs above
+`vlmc_linear_fwd_24_tiled_max_rows()`), (b) the tiled kernel that takes the weight packed (vlmc_linear_fwd_24_tiled / _48_tiled), (c) the
+dense kernel on an unpacked weight that already exists (the floor, for orientation).  (a) and (b) are compared bit for bit before
+anything is timed.  The last lines give, per row count, whether (b) beats (a) by more than the larger spread on EVERY shape, and the
+largest ladder value up to which it does: the rule VLMC_LINEAR_NM_TILED_MAX_ROWS is set by (profiles/linear_nm_tiled.md).
+    python tools/bench_linear24.py --tiled --format 24 --out <file>;  python tools/bench_linear24.py --tiled --format 48 --out <file>
 (`--format 48 --rows 1,2,4,8,16,32,48,64,128 --out <file>` gives the table of profiles/linear48.md; `--format bm --out <file>` that of
 profiles/linearbm.md, measured on a build whose VLMC_LINEARBM_MAX_ROWS is 64 so that the packed kernel is timed at every candidate limit)"""
 import argparse
@@ -28,6 +36,8 @@ from vlmc import _lib, ops  # noqa: E402
 SHAPES = {"v7b.qkvo": (4096, 4096), "v7b.gate_up": (11008, 4096), "v7b.down": (4096, 11008), "t5.qkvo": (2048, 2048), "t5.wi": (5120, 2048),
           "t5.wo": (2048, 5120)}
 ROWS = (1, 8, 16, 32, 64, 128, 512, 4096)
+VIT_SHAPES = {"vit.qkv": (4224, 1408), "vit.proj": (1408, 1408), "vit.fc1": (6144, 1408), "vit.fc2": (1408, 6144)}      # ViT-g, --tiled
+LADDER = (65, 128, 257, 512, 1024, 2048, 4096)
 CACHE = 256 << 20
 DEV = "cuda:0"
 
@@ -81,19 +91,85 @@ def med_spread(v):
     return statistics.median(v), max(v) - min(v)
 
 
+def tiled_main(args):
+    """--tiled: the unpack route, the tiled packed kernel and the dense kernel at the prefill row counts"""
+    assert args.format in ("24", "48"), "--tiled: the two n:m formats"
+    n_keep, n_of = (2, 4) if args.format == "24" else (4, 8)
+    pack, packed_fwd = getattr(ops, "pack_" + args.format), getattr(ops, "linear_fwd_" + args.format)
+    rows = [int(r) for r in args.rows.split(",")] if args.rows else list(LADDER)
+    lines = [f"format {n_keep}:{n_of} (`vlmc_linear_fwd_{args.format}_tiled`); fp16; cold weights; graph clock, us per call; median of {args.repeats} "
+             "(spread = max - min); tiled wins = its median is below the unpack route's by more than the larger of the two spreads",
+             "",
+             "| shape (N x K) | M | (a) unpack route us (spread) | (b) tiled us (spread) | (c) dense us (spread) | (b) / (a) | (b) / (c) | tiled wins |",
+             "|---|---|---|---|---|---|---|---|"]
+    print("\n".join(lines), flush=True)
+    wins = {M: [] for M in rows}
+    for name, (N, K) in {**SHAPES, **VIT_SHAPES}.items():
+        if args.only and args.only not in name:
+            continue
+        g = torch.Generator(device=DEV).manual_seed(0)
+        W = (torch.randn(N, K, device=DEV, generator=g) * 0.02).half()
+        sq = torch.rand(K, device=DEV, generator=g) + 0.5
+        keep, _ = ops.wanda_select(W, sq, "nm", n=n_keep, m=n_of)
+        packed = pack(W, keep)
+        W = getattr(ops, "unpack_" + args.format)(*packed, want_mask=False)[0]      # the weight the packed bytes stand for
+        packed_bytes = sum(t.numel() * t.element_size() for t in packed)
+        pool = 2 * CACHE // packed_bytes + 1           # a round of the packed set holds more than twice the cache; the dense set more
+        Ps, Ws = [tuple(t.clone() for t in packed) for _ in range(pool)], [W.clone() for _ in range(pool)]
+        del keep
+        for M in rows:
+            x = torch.randn(M, K, device=DEV, generator=g).half()
+            a, b = packed_fwd(x, *packed, unpack=True), packed_fwd(x, *packed, tiled=True)
+            assert torch.equal(a.view(torch.int16), b.view(torch.int16)), (name, M)
+            assert torch.equal(a.view(torch.int16), ops.linear_fwd(x, W).view(torch.int16)), (name, M)
+            del a, b
+            calls = {"unpack": lambda i: packed_fwd(x, *Ps[i], unpack=True), "tiled": lambda i: packed_fwd(x, *Ps[i], tiled=True),
+                     "dense": lambda i: ops.linear_fwd(x, Ws[i])}
+            graphs = {k: make_graph(f, pool) for k, f in calls.items()}
+            t = {k: [] for k in calls}
+            for _ in range(args.repeats):                                   # the routes alternate inside every repeat
+                for k in calls:
+                    t[k].append(graph_us(graphs[k], pool))
+            (u, su), (ti, st), (d, sd) = (med_spread(t[k]) for k in ("unpack", "tiled", "dense"))
+            win = ti < u - max(su, st)
+            wins[M].append(win)
+            line = (f"| {name} {N} x {K} | {M} | {u:.1f} ({su:.1f}) | {ti:.1f} ({st:.1f}) | {d:.1f} ({sd:.1f}) | {ti / u:.2f} | {ti / d:.2f} | "
+                    f"{'yes' if win else 'no'} |")
+            print(line, flush=True)
+            lines.append(line)
+            del graphs
+        del Ps, Ws
+        torch.cuda.empty_cache()
+    limit = 0
+    for M in rows:                                     # the largest ladder value with a win on every shape at it and at every one below
+        if not (wins[M] and all(wins[M])):
+            break
+        limit = M
+    tail = ["", "tiled wins on every shape: " + ", ".join(f"M = {M}: {sum(wins[M])} of {len(wins[M])}" for M in rows),
+            f"largest row count up to which it wins on every shape, in this format: {limit}"]
+    print("\n".join(tail), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines + tail) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
-    ap.add_argument("--rows", default=",".join(map(str, ROWS)))
+    ap.add_argument("--rows", default="")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default="")
     ap.add_argument("--format", default="24", choices=("24", "48", "bm"), help="the packed format: 2:4 selectors, 4:8 bit masks or the bitmap of any mask")
     ap.add_argument("--density", type=float, default=0.5, help="--format bm: the share of every row's columns that is kept")
+    ap.add_argument("--tiled", action="store_true", help="formats 24 / 48: the unpack route, the tiled packed kernel and the dense kernel at the "
+                    "prefill row counts " + ",".join(map(str, LADDER)))
     args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_linear24.py measures on the GPU only"
+    if args.tiled:
+        return tiled_main(args)
     n_keep, n_of = (2, 4) if args.format == "24" else (4, 8)
     pack, packed_fwd = getattr(ops, "pack_" + args.format), getattr(ops, "linear_fwd_" + args.format)
-    assert torch.cuda.is_available(), "bench_linear24.py measures on the GPU only"
-    rows = [int(r) for r in args.rows.split(",")]
+    rows = [int(r) for r in args.rows.split(",")] if args.rows else list(ROWS)
     max_rows = ops.linear_fwd_bm_max_rows() if args.format == "bm" else ops.linear_fwd_24_max_rows()
     what = f"unstructured, {args.density:g} of every row kept" if args.format == "bm" else f"{n_keep}:{n_of}"
     lines = [f"format {what} (`vlmc_linear_fwd_{args.format}`); max_rows of this build: {max_rows}; fp16; median of {args.repeats} (spread = max - min); "

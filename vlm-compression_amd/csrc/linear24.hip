@@ -25,13 +25,16 @@
 // the same bits.
 //
 // M > vlmc_linear_fwd_24_max_rows() (prefill, the vision tower): compute-bound, so the entry point unpacks into the caller's
-// workspace (unpack24_kernel / unpack48_kernel) and runs the dense launch -- the same bits by construction.
+// workspace (unpack24_kernel / unpack48_kernel) and runs the dense launch -- the same bits by construction.  The entry points
+// vlmc_linear_fwd_24_tiled / _48_tiled take any M without a workspace: the tiled GEMM of gemm_nt.hip with the weight operand packed
+// (expanded between the global load and the LDS store), again the same bits.
 //
 // The third format is the bitmap format of packbm.hip (ANY mask: values [nnz + 16], meta [N, K / 8], offs [N, ceil(K / 32)],
 // rowptr [N + 1]), entry point vlmc_linear_fwd_bm with a row limit of its own: the same kernel, chain, carry tiles and epilogue; its
 // expansion policy ExpandBM brings its own loads (a chunk is 0 to 8 halfwords at an arbitrary 2-byte offset whose address comes from
 // the metadata, which is therefore fetched one batch further ahead than the values) and its own batch registers.
 #include "common.hpp"
+#include "expand_nm.hpp"
 #include "mfma.hpp"
 
 // rows of X the packed kernel takes: chosen from tools/bench_linear24.py (profiles/linear24.md); a multiple of 16 in 16..64
@@ -46,9 +49,20 @@ static_assert(VLMC_LINEAR24_MAX_ROWS % 16 == 0 && VLMC_LINEAR24_MAX_ROWS >= 16 &
 #endif
 static_assert(VLMC_LINEARBM_MAX_ROWS % 16 == 0 && VLMC_LINEARBM_MAX_ROWS >= 16 && VLMC_LINEARBM_MAX_ROWS <= 64, "16, 32, 48 or 64");
 
+// most rows of X the Python wrappers give to the TILED packed kernel (gemm_nt.hip: gemm_nt_kernel<.., PackedNM<..>>, both n:m formats) above
+// VLMC_LINEAR24_MAX_ROWS: chosen from tools/bench_linear24.py --tiled (profiles/linear_nm_tiled.md); 0 = never, else >= that limit
+#ifndef VLMC_LINEAR_NM_TILED_MAX_ROWS
+#define VLMC_LINEAR_NM_TILED_MAX_ROWS 0
+#endif
+static_assert(VLMC_LINEAR_NM_TILED_MAX_ROWS == 0 || VLMC_LINEAR_NM_TILED_MAX_ROWS >= VLMC_LINEAR24_MAX_ROWS, "0 (never) or at least the packed kernel's own limit");
+
 namespace vlmc {
 
 constexpr int L24_WAVES = 16;
+
+// gemm_nt.hip: the register-staged tiled GEMM with the weight operand packed n:m (fmt 24 or 48), arguments checked here
+int linear_nm_tiled_launch(const char *fn, int fmt, const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype,
+                           int64_t M, int64_t N, int64_t K, int64_t ldx, void *Y, int64_t ldy, void *stream);
 
 struct Linear24Args {
     const uint16_t *X;            // [M, K], row stride ldx
@@ -65,21 +79,8 @@ struct LinearBMArgs : Linear24Args {                                 // values: 
     int64_t nnz;
 };
 
-// one pack chunk -> the 8 weights of the A fragment.  Per group of four: code = i0 | i1 << 2 (i0 < i1), the two kept values go
-// to positions i0 and i1, the others are +0.  Two 2-bit indices cannot address outside their group.
-__device__ __forceinline__ u32x4_t expand24(const u32x2_t v, const uint32_t code) {
-    u32x4_t w;
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        const uint32_t c = code >> (4 * g);
-        const uint64_t lo = uint64_t(v[g] & 0xffffu) << (16 * (c & 3u)), hi = uint64_t(v[g] >> 16) << (16 * ((c >> 2) & 3u));
-        const uint64_t grp = lo | hi;
-        w[2 * g] = uint32_t(grp), w[2 * g + 1] = uint32_t(grp >> 32);
-    }
-    return w;
-}
-
-// The expansion policies: how the packed bytes of one chunk become the 8 weights of the A fragment.  A policy owns its loads and
+// The expansion policies: how the packed bytes of one chunk become the 8 weights of the A fragment (expand_nm.hpp: expand24,
+// perm_selector and the selector table).  A policy owns its loads and
 // its batch registers:
 //   Args         the kernel's arguments (Linear24Args, or more)
 //   steps<MT>()  the K-steps of a batch -- what a wave holds in registers at MT tiles of X
@@ -117,19 +118,6 @@ struct Expand24 : ExpandNM {
     template <int D> __device__ __forceinline__ u32x4_t expand(const Regs<D> &R, int d) const { return expand24(R.v[d], R.code[d]); }
 };
 
-// Selector dword d (positions 2d, 2d + 1) of bitmap byte e for v_perm_b32 over the value halfwords base .. base + 3: bit p of e
-// says that position p holds the next value, value r = popcount of the bits below p.  A position whose value is one of the four
-// gets that halfword's two bytes, every other position 0x0c0c (v_perm_b32's constant 0x00).
-__device__ __forceinline__ uint32_t perm_selector(uint32_t e, uint32_t d, uint32_t base) {
-    uint32_t s = 0x0c0c0c0cu;
-#pragma unroll
-    for (uint32_t h = 0; h < 2; ++h) {
-        const uint32_t p = 2 * d + h, r = uint32_t(__popc(e & ((1u << p) - 1u))) - base;   // position p takes value base + r
-        if (((e >> p) & 1u) && r < 4) s = (s & ~(0xffffu << (16 * h))) | ((2 * r) | (2 * r + 1) << 8) << (16 * h);
-    }
-    return s;
-}
-
 // 4:8: bit j of the byte says that position j holds the next value.  The chunk's 8 bytes are exactly the sources of v_perm_b32
 // ({v[1], v[0]}: selector s picks byte s of the chunk, 0x0c gives 0x00), so each output dword is one perm whose selector comes
 // from a table byte -> four selector dwords (4 KiB of LDS, filled here).  A selector never names anything but a byte of the
@@ -139,19 +127,14 @@ struct Expand48 : ExpandNM {
     const u32x4_t *sel;
     __device__ __forceinline__ void init(int tid) {
         __shared__ u32x4_t table[256];
-        reinterpret_cast<uint32_t *>(table)[tid] = perm_selector(uint32_t(tid) >> 2, uint32_t(tid) & 3u, 0);   // 256 entries x 4 dwords
+        fill_perm_table<64 * L24_WAVES, 0>(reinterpret_cast<uint32_t *>(table), tid);   // 256 entries x 4 dwords
         sel = table;
     }
     template <int D> __device__ __forceinline__ u32x4_t expand(const Regs<D> &R, int d) const {
-        const u32x2_t v = R.v[d];
-        const u32x4_t s = sel[R.code[d] & 0xffu];
-        u32x4_t w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = __builtin_amdgcn_perm(v[1], v[0], s[j]);
-        return w;
+        return expand48(R.v[d], sel[R.code[d] & 0xffu]);
     }
 };
-static_assert(64 * L24_WAVES == 256 * 4, "Expand48 / ExpandBM::init: one thread per selector dword");
+static_assert(64 * L24_WAVES == 256 * 4, "Expand48 / ExpandBM::init: one thread per selector dword (fill_perm_table<1024>)");
 
 // bm: the byte means what the 4:8 byte means, with 0 to 8 bits set.  The chunk's values are the 0 to 8 halfwords from index
 //     i = min(rowptr[n] + offs[n][s] + popcount(the step's meta bytes before this quarter), nnz)
@@ -184,8 +167,8 @@ struct ExpandBM {
     static __device__ __forceinline__ const uint16_t *spare(const Args &a) { return a.offs; }
     __device__ __forceinline__ void init(int tid) {
         __shared__ u32x4_t table[512];
-        reinterpret_cast<uint32_t *>(table)[tid] = perm_selector(uint32_t(tid) >> 2, uint32_t(tid) & 3u, 0);
-        reinterpret_cast<uint32_t *>(table)[1024 + tid] = perm_selector(uint32_t(tid) >> 2, uint32_t(tid) & 3u, 4);
+        fill_perm_table<64 * L24_WAVES, 0>(reinterpret_cast<uint32_t *>(table), tid);
+        fill_perm_table<64 * L24_WAVES, 4>(reinterpret_cast<uint32_t *>(table) + 1024, tid);
         sel = table;
     }
     __device__ __forceinline__ void row(const Args &a, int wrow, int fq) {
@@ -409,6 +392,27 @@ extern "C" int vlmc_linear_fwd_48(const void *X, const void *values, const uint8
                                   int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace, size_t workspace_bytes, void *stream) {
     return linear_packed_fwd<Expand48>("vlmc_linear_fwd_48", vlmc_unpack_48, X, values, meta, bias, dtype, M, N, K, ldx, Y, ldy, workspace,
                                        workspace_bytes, stream);
+}
+
+// the tiled kernel at any M: no workspace, no row limit of its own
+static int linear_nm_tiled(const char *fn, int fmt, const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M,
+                           int64_t N, int64_t K, int64_t ldx, void *Y, int64_t ldy, void *stream) {
+    const int ok = linear_packed_check(fn, X, values, meta, dtype, M, N, K, ldx, Y, ldy);
+    if (ok != VLMC_OK) return ok;
+    VLMC_REQUIRE(aligned16(X) && (reinterpret_cast<uintptr_t>(values) & 7u) == 0, "%s: X must be 16-byte, values 8-byte aligned", fn);
+    return linear_nm_tiled_launch(fn, fmt, X, values, meta, bias, dtype, M, N, K, ldx, Y, ldy, stream);
+}
+
+extern "C" int vlmc_linear_fwd_24_tiled_max_rows(void) { return VLMC_LINEAR_NM_TILED_MAX_ROWS; }
+
+extern "C" int vlmc_linear_fwd_24_tiled(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
+                                        int64_t K, int64_t ldx, void *Y, int64_t ldy, void *stream) {
+    return linear_nm_tiled("vlmc_linear_fwd_24_tiled", 24, X, values, meta, bias, dtype, M, N, K, ldx, Y, ldy, stream);
+}
+
+extern "C" int vlmc_linear_fwd_48_tiled(const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype, int64_t M, int64_t N,
+                                        int64_t K, int64_t ldx, void *Y, int64_t ldy, void *stream) {
+    return linear_nm_tiled("vlmc_linear_fwd_48_tiled", 48, X, values, meta, bias, dtype, M, N, K, ldx, Y, ldy, stream);
 }
 
 extern "C" int vlmc_linear_fwd_bm(const void *X, const void *values, const uint8_t *meta, const uint16_t *offs, const int64_t *rowptr, int64_t nnz,

@@ -84,6 +84,9 @@ SIGNATURES = {
     "vlmc_pack_48": (_i, [_p, _i, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p]),
     "vlmc_unpack_48": (_i, [_p, _p, _i, _i64, _i64, _p, _i64, _p, _i64, _p, _p]),
     "vlmc_linear_fwd_48": (_i, [_p, _p, _p, _p, _i, _i64, _i64, _i64, _i64, _p, _i64, _p, _sz, _p]),
+    "vlmc_linear_fwd_24_tiled_max_rows": (_i, []),
+    "vlmc_linear_fwd_24_tiled": (_i, [_p, _p, _p, _p, _i, _i64, _i64, _i64, _i64, _p, _i64, _p]),
+    "vlmc_linear_fwd_48_tiled": (_i, [_p, _p, _p, _p, _i, _i64, _i64, _i64, _i64, _p, _i64, _p]),
     "vlmc_pack_bm_rows": (_i, [_p, _i64, _i64, _i64, _p, _p]),
     "vlmc_pack_bm": (_i, [_p, _i, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p]),
     "vlmc_unpack_bm": (_i, [_p, _p, _p, _p, _i64, _i, _i64, _i64, _p, _i64, _p, _i64, _p, _p]),

@@ -698,6 +698,13 @@ def linear_fwd_24_max_rows() -> int:
     return int(_lib.load().vlmc_linear_fwd_24_max_rows())
 
 
+def linear_fwd_24_tiled_max_rows() -> int:
+    """Most rows of x that `linear_fwd_24` / `linear_fwd_48` give to the TILED packed kernel (vlmc_linear_fwd_24_tiled_max_rows; both
+    formats): between `linear_fwd_24_max_rows()` and this the weight is expanded on its way into LDS and no scratch weight exists;
+    above, the unpack route.  0: never by default (`tiled=True` still selects it)."""
+    return int(_lib.load().vlmc_linear_fwd_24_tiled_max_rows())
+
+
 def linear_fwd_24_supported(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None) -> bool:
     """Whether `linear_fwd_24` takes this call: 16-bit x [.., K] and contiguous values [N, K / 2] of one dtype, meta [N, K / 8]
     uint8 contiguous, all on the GPU, K a multiple of 8."""
@@ -735,32 +742,49 @@ def _linear_fwd_packed(tag, x, N, K, bias, unpack, packed, workspace):
     return y.reshape(*x.shape[:-1], N)
 
 
-def _linear_fwd_nm(f, x, values, meta, bias, unpack):
+def _linear_fwd_nm(f, x, values, meta, bias, unpack, tiled):
+    if unpack and tiled:
+        raise ValueError(f"vlmc.linear_fwd_{f['tag']}: unpack=True and tiled=True name two different routes")
     _need_gpu(x, values, meta, bias)
     if not linear_fwd_24_supported(x, values, meta, bias):
         raise TypeError(f"vlmc.linear_fwd_{f['tag']}: fp16/bf16 x [.., K], contiguous values [N, K / 2] of the same dtype, meta [N, K / 8] uint8 "
                         "(K % 8 == 0) and a contiguous bias [N] of that dtype expected")
+    N, K = values.shape[0], 2 * values.shape[1]
+    rows = x.numel() // K
+    if tiled is None:                                       # the rule: above the carried-chain kernel's rows, up to the measured limit
+        tiled = not unpack and linear_fwd_24_max_rows() < rows <= linear_fwd_24_tiled_max_rows()
+    if tiled and rows:
+        x2, M, ld = _rows(x, K, aligned=True)
+        y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+        _lib.check(getattr(_lib.load(), f"vlmc_linear_fwd_{f['tag']}_tiled")(x2.data_ptr(), values.data_ptr(), meta.data_ptr(),
+                                                                              bias.data_ptr() if bias is not None else None, _DT[x.dtype], M, N, K,
+                                                                              ld, y.data_ptr(), N, _stream()))
+        return y.reshape(*x.shape[:-1], N)
     return _linear_fwd_packed(f["tag"], x, values.shape[0], 2 * values.shape[1], bias, unpack, (values.data_ptr(), meta.data_ptr()),
                               "vlmc_linear_fwd_24_workspace")
 
 
 def linear_fwd_24(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None,
-                  unpack: bool = False) -> torch.Tensor:
+                  unpack: bool = False, tiled: bool | None = None) -> torch.Tensor:
     """y = x @ unpack_24(values, meta).T + bias computed FROM the packed weight (vlmc_linear_fwd_24): bit for bit
     `linear_fwd(x, unpack_24(values, meta)[0], bias)`, any leading dims.  Up to `linear_fwd_24_max_rows()` rows one kernel reads
     the packed bytes and expands them in registers; more rows (prefill) unpack into a per-device scratch weight and run the dense
     kernel.  `meta` is trusted (`pack_24` wrote it, or `formats.load_packed_24` validated it).  `unpack`: the unpack route
-    whatever the number of rows (the cross-check of the packed kernel)."""
-    return _linear_fwd_nm(_FMT24, x, values, meta, bias, unpack)
+    whatever the number of rows (the cross-check of the packed kernel).  `tiled`: the tiled GEMM that takes the weight operand packed
+    (vlmc_linear_fwd_24_tiled: any number of rows, no scratch weight, the same bits) -- None: for more than `linear_fwd_24_max_rows()` and
+    at most `linear_fwd_24_tiled_max_rows()` rows; True: whatever the number of rows (its cross-check; with `unpack` it raises); False:
+    never."""
+    return _linear_fwd_nm(_FMT24, x, values, meta, bias, unpack, tiled)
 
 
 def linear_fwd_48(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None,
-                  unpack: bool = False) -> torch.Tensor:
+                  unpack: bool = False, tiled: bool | None = None) -> torch.Tensor:
     """y = x @ unpack_48(values, meta).T + bias computed FROM the packed 4:8 weight (vlmc_linear_fwd_48): bit for bit
     `linear_fwd(x, unpack_48(values, meta)[0], bias)`, any leading dims; `linear_fwd_24`'s routes, row limit
     (`linear_fwd_24_max_rows()`) and scratch weight.  `meta` is trusted (`pack_48` wrote it, or `formats.load_packed_48`
-    validated it).  `unpack`: the unpack route whatever the number of rows (the cross-check of the packed kernel)."""
-    return _linear_fwd_nm(_FMT48, x, values, meta, bias, unpack)
+    validated it).  `unpack`: the unpack route whatever the number of rows (the cross-check of the packed kernel).  `tiled`: as in
+    `linear_fwd_24` (vlmc_linear_fwd_48_tiled; the limit `linear_fwd_24_tiled_max_rows()` answers for both formats)."""
+    return _linear_fwd_nm(_FMT48, x, values, meta, bias, unpack, tiled)
 
 
 # ---- the bitmap format (csrc/packbm.hip): any mask ------------------------------------------------------------------------------
