@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VLMC_ABI_VERSION 27
+#define VLMC_ABI_VERSION 28
 
 #define VLMC_OK 0
 #define VLMC_EINVAL (-1)     /* bad argument (shape, dtype, alignment, null pointer) */
@@ -432,6 +432,19 @@ int vlmc_row_mean(const float *x, int64_t rows, int64_t n, int64_t ldx, float *o
  * elements, nothing rounded to 16 bits.                                                                                          */
 int vlmc_gelu(const void *x, void *y, int64_t n, int dtype, int tanh_approx, void *stream);
 
+/* T5 v1.1's gated product `self.act(self.wi_0(h)) * self.wi_1(h)` (modeling_t5.py:337-341) in one pass instead of vlmc_gelu plus
+ * torch's `mul`: five tensor passes become three.  Per element, every step a value of its own as in the two ops it replaces:
+ *     out = rnd(f32(rnd(gelu(f32(x)))) * f32(y))      gelu: vlmc_gelu's arithmetic; rnd: one rounding to the dtype (torch's 16-bit
+ *                                                     mul: opmath float; a NaN product is torch's bf16 NaN 0x7FC0)
+ * so the bits are those of `vlmc_gelu` followed by `torch.mul`.  dtype VLMC_F16 / VLMC_BF16.  x, y, out: [rows, cols] with row
+ * pitches ldx / ldy / ldo in elements (>= cols) -- column slices of one buffer or tensors of their own; 16-byte accesses when every
+ * pointer is 16-byte aligned and every pitch a multiple of 8, element by element otherwise (the same bits).  out overlaps neither x nor y.
+ * rowmap (may be NULL: every row is computed, n_real ignored): the int32 [rows] map vlmc_linear_fwd_rows takes -- rows
+ * rowmap[0 .. n_real) are computed, rows rowmap[n_real .. rows) of out are written as zeros and x / y are not read there: whatever
+ * the padding rows of the inputs hold (NaN included) reaches nothing, and a padded group's padding stays zero.               */
+int vlmc_gelu_mul(const void *x, const void *y, void *out, int dtype, int tanh_approx, int64_t rows, int64_t cols, int64_t ldx,
+                  int64_t ldy, int64_t ldo, const int32_t *rowmap, int64_t n_real, void *stream);
+
 /* Row-wise softmax over the last dimension, PADDING-invariant: `F.softmax(scores.float(), dim=-1)` (modeling_t5.py:604-606),
  * `attn.softmax(dim=-1)` on 16-bit scores (eva_vit.py:158), `nn.Softmax(dim=-1)(scores)` (Qformer.py:228) during a replay.
  * fp32 arithmetic in ONE fixed order (csrc/softmax_order.hpp): the maximum; e_j = expf(x_j - max); 16 class sums (class =
@@ -487,6 +500,23 @@ int vlmc_attn_fwd_clamp(const void *Q, const void *K, const void *V, void *O, in
                         int64_t Tk, int64_t head_dim, const int64_t *q_strides, const int64_t *k_strides, const int64_t *v_strides,
                         int has_mul, float mul, const void *add0, const int64_t *add0_strides, const void *add1,
                         const int64_t *add1_strides, float clamp_min, const int32_t *q_len, const int32_t *k_len, void *stream);
+
+/* vlmc_attn_fwd_lens on the operands AS THE QKV LINEAR WROTE THEM: the reference's EVA attention (eva_vit.py:133-141)
+ *     qkv = F.linear(x, self.qkv.weight, torch.cat((self.q_bias, zeros, self.v_bias)));  q, k, v = its slices;  q = q * self.scale
+ * spends a broadcast add over [B, N, 3 C] and a multiply over [B, H, N, d] only to hand this kernel its operands.  Here the kernel
+ * applies them where it stages K, V and the Q fragments, each step one rounding to the dtype like the tensor op it stands for:
+ *     q' = rnd(f32(rnd(f32(q) + f32(q_add))) * q_mul)     k' = rnd(f32(k) + f32(k_add))     v' = rnd(f32(v) + f32(v_add))
+ * q_add / k_add / v_add: NULL (no op -- not `+ 0`) or 16-bit, 2-byte aligned, element [h][e] at h * stride_h + e for e < head_dim,
+ * broadcast over batch and token (slices of the model's bias vector); has_q_mul / q_mul: a finite fp32 scalar applied after q_add.
+ * From there on the chain is vlmc_attn_fwd's: the output has the bits of vlmc_attn_fwd_lens on the materialised operands.  K and V
+ * with an addend are staged through registers.  At most ONE score addend (add1 must be NULL); has_clamp must be 0 -- the clamp
+ * variant has no pre-op instantiation and is refused with VLMC_EINVAL.  With every pre-op absent this is vlmc_attn_fwd_lens. */
+int vlmc_attn_fwd_pre(const void *Q, const void *K, const void *V, void *O, int dtype, int64_t batch, int64_t heads, int64_t Tq,
+                      int64_t Tk, int64_t head_dim, const int64_t *q_strides, const int64_t *k_strides, const int64_t *v_strides,
+                      int has_mul, float mul, const void *add0, const int64_t *add0_strides, const void *add1,
+                      const int64_t *add1_strides, int has_clamp, float clamp_min, const int32_t *q_len, const int32_t *k_len,
+                      const void *q_add, int64_t q_add_stride_h, const void *k_add, int64_t k_add_stride_h, const void *v_add,
+                      int64_t v_add_stride_h, int has_q_mul, float q_mul, void *stream);
 
 /* ---- the rotary position embedding of a LLaMA attention, q and k in one launch ----------------------------------------------
  * Replaces `apply_rotary_pos_emb(q, k, cos, sin, position_ids)`, modeling_llama.py:126-140 (with `rotate_half`, :126-130): two

@@ -1,4 +1,5 @@
-"""vlmc_attn_fwd against the unfused chain on this library's kernels and against vlmc_sdpa_fwd, at the shapes of a prune (us per call)."""
+"""vlmc_attn_fwd against the unfused chain on this library's kernels and against vlmc_sdpa_fwd, at the shapes of a prune (us per call).
+`--pre`: also the ViT-g attention front -- torch's qkv-bias add and q scale plus the kernel against vlmc_attn_fwd_pre on the raw slices."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "vlm-compression_amd"))
@@ -54,3 +55,39 @@ for name, dt, B, H, Tq, Tk, d, nadd, f32 in SHAPES:
     except Exception:
         ts = float("nan")
     print(f"| {name} [{B}, {H}, {Tq}, {Tk}, {d}] | {tf:.1f} | {tu:.1f} | {ts:.1f} | {B * H * Tq * Tk * 2 / 1e6:.0f} |", flush=True)
+
+# ---- the ViT-g attention front (eva_vit.py:133-141): torch's bias add and q scale in front of the kernel against vlmc_attn_fwd_pre --
+# `--pre` only: repeated, so that the spread of a route shows next to the difference between the routes
+if "--pre" in sys.argv:
+    import numpy as np
+    B, H, N, d, dt = 128, 16, 257, 88, torch.float16
+    C = H * d
+    y = (torch.randn(B, N, 3 * C, device=dev) * 0.5).to(dt)
+    bias = torch.cat(((torch.randn(C, device=dev) * 0.5).to(dt), torch.zeros(C, device=dev, dtype=dt), (torch.randn(C, device=dev) * 0.5).to(dt)))
+    scale = d ** -0.5
+    qmul = float(np.float32(scale))
+
+    def slices(t):
+        t = t.reshape(B, N, 3, H, -1).permute(2, 0, 3, 1, 4)
+        return t[0], t[1], t[2]
+
+    def materialized():
+        q, k, v = slices(y + bias)
+        return ops.attn_fused(q * scale, k, v)
+    q0, k0, v0 = slices(y)
+    kw = dict(q_add=bias[:C].view(H, d), k_add=bias[C:2 * C].view(H, d), v_add=bias[2 * C:].view(H, d), q_mul=qmul)
+    assert torch.equal(materialized(), ops.attn_fused(q0, k0, v0, **kw))
+    qm, km, vm = slices(y + bias)
+    qm = qm * scale
+    nbytes = {"add": 2 * B * N * 3 * C * 2, "mul": 2 * B * N * C * 2}
+    print(f"\nViT-g attention front [{B}, {H}, {N}, {N}, {d}] fp16; `qkv + bias` moves {nbytes['add'] / 1e6:.0f} MB, `q * scale` {nbytes['mul'] / 1e6:.0f} MB (8 TB/s HBM peak)")
+    print("| run | kernel on materialized operands us | torch add us (TB/s) | torch mul us (TB/s) | add + mul + kernel us | vlmc_attn_fwd_pre us | kernel without pre-ops on the packed slices us |")
+    print("|---|---|---|---|---|---|---|")
+    for r in range(5):
+        t_k = timeit(lambda: ops.attn_fused(qm, km, vm), 50)
+        t_a = timeit(lambda: y + bias, 50)
+        t_m = timeit(lambda: q0 * scale, 50)
+        t_all = timeit(materialized, 50)
+        t_p = timeit(lambda: ops.attn_fused(q0, k0, v0, **kw), 50)
+        t_0 = timeit(lambda: ops.attn_fused(q0, k0, v0), 50)
+        print(f"| {r} | {t_k:.1f} | {t_a:.1f} ({nbytes['add'] / t_a / 1e6:.2f}) | {t_m:.1f} ({nbytes['mul'] / t_m / 1e6:.2f}) | {t_all:.1f} | {t_p:.1f} | {t_0:.1f} |", flush=True)

@@ -50,6 +50,14 @@ struct AttnArgs {
     // caller vouches that every key behind them is masked out by an addend (probability exactly 0): their tiles are neither staged nor
     // multiplied; qlen[b] = its real queries: the rows behind them are written as zeros, not computed
     const int32_t *qlen, *klen;
+    // PRE instantiations (vlmc_attn_fwd_pre): the operands as the qkv linear wrote them.  Nullable addends, element [h][e] at
+    // h * s?a_h + e, broadcast over batch and token (slices of the model's bias vector), and a multiplier for q after its addend:
+    //     q' = wd(float(wd(float(q) + float(qadd))) * qmul),  k' = wd(float(k) + float(kadd)),  v' = wd(float(v) + float(vadd))
+    // applied where the operands are staged; a null addend is no op.  K and V with an addend are staged through registers (dma = 0).
+    const uint16_t *qadd, *kadd, *vadd;
+    int64_t sqa_h, ska_h, sva_h;
+    int has_qmul;
+    float qmul;
 };
 
 typedef short af_s16x4_t __attribute__((ext_vector_type(4)));
@@ -69,13 +77,42 @@ __device__ __forceinline__ U16x4 attn_bias4(const uint16_t *row, int key0, int T
     return r;
 }
 
+// 8 operand elements plus 8 addend elements / times a multiplier: each result an fp32 value of its own, rounded to the dtype once --
+// the tensor ops `qkv + bias` and `q * scale` (eva_vit.py:133-141) on these elements
+template <typename T> __device__ __forceinline__ u32x4_t attn_pre_add8(u32x4_t v, const uint16_t *add) {
+    const u32x4_t av = load16_a2(add);
+    uint16_t e[8], b[8];
+    __builtin_memcpy(e, &v, 16);
+    __builtin_memcpy(b, &av, 16);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float t = ieee_add(to_f32<T>(e[j]), to_f32<T>(b[j]));
+        asm volatile("" : "+v"(t));
+        e[j] = from_f32<T>(t);
+    }
+    __builtin_memcpy(&v, e, 16);
+    return v;
+}
+template <typename T> __device__ __forceinline__ u32x4_t attn_pre_mul8(u32x4_t v, float m) {
+    uint16_t e[8];
+    __builtin_memcpy(e, &v, 16);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float t = ieee_mul(to_f32<T>(e[j]), m);
+        asm volatile("" : "+v"(t));
+        e[j] = from_f32<T>(t);
+    }
+    __builtin_memcpy(&v, e, 16);
+    return v;
+}
+
 // DS = K-steps of 32 along d; MAXKT = 16-key tiles a head may have (the scores of a block of queries are registers); NW = waves
 // per workgroup: 8 where a head's K and V leave room for one workgroup per CU only (two waves per SIMD: one wave's softmax runs
 // on the vector pipe while the other's products run on the matrix pipe)
 // NADD = addends (0, 1, 2): their prefetched entries are registers.  MINW = waves per SIMD the register budget is held to.
 // CLAMP: `torch.max(scores, torch.tensor(torch.finfo(dtype).min))` between the addends and the softmax (modeling_llama.py:235-236:
-// mask + mask may be -inf in fp16); the other instantiations do not contain the step.
-template <typename T, int DS, int MAXKT, int NW, int NADD, int MINW, bool CLAMP = false>
+// mask + mask may be -inf in fp16); the other instantiations do not contain the step.  PRE: the operand pre-ops of AttnArgs, likewise.
+template <typename T, int DS, int MAXKT, int NW, int NADD, int MINW, bool CLAMP = false, bool PRE = false>
 __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArgs a) {
     constexpr int DP = 32 * DS, RS = DP * 2 + 16, DT = 2 * DS, NT = 64 * NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -118,6 +155,10 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArg
                 const bool in = i < total && r < Tk && ch * 8 < a.d;
                 kv[j] = in ? load16_a2(Kp + int64_t(r) * a.sk_t + ch * 8) : zero;
                 vv[j] = in ? load16_a2(Vp + int64_t(r) * a.sv_t + ch * 8) : zero;
+                if constexpr (PRE) {                                          // (rows past Tk and columns past d stay zero)
+                    if (in && a.kadd != nullptr) kv[j] = attn_pre_add8<T>(kv[j], a.kadd + int64_t(h) * a.ska_h + ch * 8);
+                    if (in && a.vadd != nullptr) vv[j] = attn_pre_add8<T>(vv[j], a.vadd + int64_t(h) * a.sva_h + ch * 8);
+                }
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -162,6 +203,10 @@ __global__ __launch_bounds__(64 * NW, MINW) void attn_fused_kernel(const AttnArg
         for (int ds = 0; ds < DS; ++ds) {
             const int e = 32 * ds + 8 * c;
             fq[ds] = e < a.d ? load16_a2(Qp + int64_t(qc) * a.sq_t + e) : u32x4_t{0u, 0u, 0u, 0u};
+            if constexpr (PRE) {
+                if (e < a.d && a.qadd != nullptr) fq[ds] = attn_pre_add8<T>(fq[ds], a.qadd + int64_t(h) * a.sqa_h + e);
+                if (e < a.d && a.has_qmul) fq[ds] = attn_pre_mul8<T>(fq[ds], a.qmul);
+            }
         }
         // ---- the addends of this block of queries: requested now, used after the first product ---------------------------
         U16x4 b0[NADD >= 1 ? MAXKT : 1], b1[NADD >= 2 ? MAXKT : 1];
@@ -314,14 +359,14 @@ static int attn_max_keys(int d) {
     return int(k > 512 ? 512 : k);
 }
 
-template <typename T, int DS, int MAXKT, int NW, int NADD, int MINW, bool CLAMP> static int attn_launch2(const AttnArgs &a, int64_t bh, hipStream_t s) {
+template <typename T, int DS, int MAXKT, int NW, int NADD, int MINW, bool CLAMP, bool PRE> static int attn_launch2(const AttnArgs &a, int64_t bh, hipStream_t s) {
     constexpr int RS = 32 * DS * 2 + 16;
     const int KT = ((a.Tk + 31) >> 5) << 1;
     const size_t lds = 2 * ((size_t(KT) * 16 * RS + 1023) & ~size_t(1023)) + NW * kAttnScratch;
     static PerDeviceOnce once;
     int dev;
     if (once.needed(&dev)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW, CLAMP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW, CLAMP, PRE>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024) != hipSuccess) {
             set_error("vlmc_attn_fwd: cannot reserve LDS");
             return VLMC_EHIP;
@@ -330,25 +375,25 @@ template <typename T, int DS, int MAXKT, int NW, int NADD, int MINW, bool CLAMP>
     }
     const dim3 grid{unsigned(bh), unsigned((a.nblk + NW * a.bpw - 1) / (NW * a.bpw))}, block{64 * NW};
     const LaunchEvents ev = take_launch_events();
-    if (ev.start || ev.stop) hipExtLaunchKernelGGL((attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW, CLAMP>), grid, block, lds, s, ev.start, ev.stop, 0, a);
-    else hipLaunchKernelGGL((attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW, CLAMP>), grid, block, lds, s, a);
+    if (ev.start || ev.stop) hipExtLaunchKernelGGL((attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW, CLAMP, PRE>), grid, block, lds, s, ev.start, ev.stop, 0, a);
+    else hipLaunchKernelGGL((attn_fused_kernel<T, DS, MAXKT, NW, NADD, MINW, CLAMP, PRE>), grid, block, lds, s, a);
     return VLMC_OK;
 }
 
-template <typename T, int DS, int NADD, bool CLAMP> static int attn_launch(const AttnArgs &a, int64_t bh, hipStream_t s) {
+template <typename T, int DS, int NADD, bool CLAMP, bool PRE> static int attn_launch(const AttnArgs &a, int64_t bh, hipStream_t s) {
     const int KT = ((a.Tk + 31) >> 5) << 1;
-    if (KT <= 4) return attn_launch2<T, DS, 4, 4, NADD, 3, CLAMP>(a, bh, s);
-    if (KT <= 8) return attn_launch2<T, DS, 8, 4, NADD, 3, CLAMP>(a, bh, s);
-    if (KT <= 12) return attn_launch2<T, DS, 12, 4, NADD, 2, CLAMP>(a, bh, s);
-    if constexpr (DS == 4) return attn_launch2<T, DS, 18, 4, NADD, 1, CLAMP>(a, bh, s);  // (head_dim 128: at most 288 keys fit, with four waves' scratch)
-    else if (KT <= 18) return attn_launch2<T, DS, 18, 8, NADD, 2, CLAMP>(a, bh, s);
-    else if constexpr (DS == 2) return attn_launch2<T, DS, 32, 8, NADD, 2, CLAMP>(a, bh, s);
-    else return attn_launch2<T, DS, 22, 8, NADD, 2, CLAMP>(a, bh, s);                    // (head_dim 96: at most 352 keys fit)
+    if (KT <= 4) return attn_launch2<T, DS, 4, 4, NADD, 3, CLAMP, PRE>(a, bh, s);
+    if (KT <= 8) return attn_launch2<T, DS, 8, 4, NADD, 3, CLAMP, PRE>(a, bh, s);
+    if (KT <= 12) return attn_launch2<T, DS, 12, 4, NADD, 2, CLAMP, PRE>(a, bh, s);
+    if constexpr (DS == 4) return attn_launch2<T, DS, 18, 4, NADD, 1, CLAMP, PRE>(a, bh, s);  // (head_dim 128: at most 288 keys fit, with four waves' scratch)
+    else if (KT <= 18) return attn_launch2<T, DS, 18, 8, NADD, 2, CLAMP, PRE>(a, bh, s);
+    else if constexpr (DS == 2) return attn_launch2<T, DS, 32, 8, NADD, 2, CLAMP, PRE>(a, bh, s);
+    else return attn_launch2<T, DS, 22, 8, NADD, 2, CLAMP, PRE>(a, bh, s);                    // (head_dim 96: at most 352 keys fit)
 }
 
 // one translation unit per (dtype, number of addends): `make -j` compiles them side by side
-template <typename T, int NADD, bool CLAMP = false> static int attn_dispatch(const AttnArgs &a, int64_t bh, int ds, hipStream_t s) {
-    return ds <= 2 ? attn_launch<T, 2, NADD, CLAMP>(a, bh, s) : ds == 3 ? attn_launch<T, 3, NADD, CLAMP>(a, bh, s) : attn_launch<T, 4, NADD, CLAMP>(a, bh, s);
+template <typename T, int NADD, bool CLAMP = false, bool PRE = false> static int attn_dispatch(const AttnArgs &a, int64_t bh, int ds, hipStream_t s) {
+    return ds <= 2 ? attn_launch<T, 2, NADD, CLAMP, PRE>(a, bh, s) : ds == 3 ? attn_launch<T, 3, NADD, CLAMP, PRE>(a, bh, s) : attn_launch<T, 4, NADD, CLAMP, PRE>(a, bh, s);
 }
 int attn_dispatch_f16_0(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
 int attn_dispatch_f16_1(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
@@ -360,5 +405,9 @@ int attn_dispatch_clamp_f16_1(const AttnArgs &a, int64_t bh, int ds, hipStream_t
 int attn_dispatch_clamp_f16_2(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
 int attn_dispatch_clamp_bf16_1(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
 int attn_dispatch_clamp_bf16_2(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
+int attn_dispatch_pre_f16_0(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);        // (with the operand pre-ops: no or one addend)
+int attn_dispatch_pre_f16_1(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
+int attn_dispatch_pre_bf16_0(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
+int attn_dispatch_pre_bf16_1(const AttnArgs &a, int64_t bh, int ds, hipStream_t s);
 
 }  // namespace vlmc

@@ -99,12 +99,15 @@ SIGNATURES = {
     "vlmc_linear_fwd_gather": (_i, [_p, _p, _p, _i, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _i64, _p]),
     "vlmc_attn_matmul": (_i, [_p, _p, _p, _i] + [_i64] * 15 + [_p]),
     "vlmc_gelu": (_i, [_p, _p, _i64, _i, _i, _p]),
+    "vlmc_gelu_mul": (_i, [_p, _p, _p, _i, _i] + [_i64] * 5 + [_p, _i64, _p]),
     "vlmc_row_mean": (_i, [_p, _i64, _i64, _i64, _p, _p]),
     "vlmc_softmax_rows": (_i, [_p, _i, _i64, _i64, _i64, _p, _i, _i64, _p]),
     "vlmc_attn_max_keys": (_i, [_i64]),
     "vlmc_attn_fwd": (_i, [_p, _p, _p, _p, _i] + [_i64] * 5 + [_p, _p, _p, _i, _c.c_float, _p, _p, _p, _p, _p]),
     "vlmc_attn_fwd_lens": (_i, [_p, _p, _p, _p, _i] + [_i64] * 5 + [_p, _p, _p, _i, _c.c_float, _p, _p, _p, _p, _p, _p, _p]),
     "vlmc_attn_fwd_clamp": (_i, [_p, _p, _p, _p, _i] + [_i64] * 5 + [_p, _p, _p, _i, _c.c_float, _p, _p, _p, _p, _c.c_float, _p, _p, _p]),
+    "vlmc_attn_fwd_pre": (_i, [_p, _p, _p, _p, _i] + [_i64] * 5 + [_p, _p, _p, _i, _c.c_float, _p, _p, _p, _p, _i, _c.c_float, _p, _p,
+                                _p, _i64, _p, _i64, _p, _i64, _i, _c.c_float, _p]),
     "vlmc_rope": (_i, [_p, _p, _p, _p, _i] + [_i64] * 4 + [_p, _p, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p]),
     "vlmc_rope_status": (_i, [_p, _p]),
     "vlmc_rms_norm": (_i, [_p, _i, _i64, _i64, _i64, _p, _c.c_float, _i, _p, _i64, _p]),

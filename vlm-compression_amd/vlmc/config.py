@@ -76,7 +76,9 @@ CROSSCHECK = {
     "VLMC_ATTN_TR": ("1", "0: attn @ v with the operand transposed while writing LDS"),
     "VLMC_LORA_FUSED": ("1", "0: SparseLoRA through a materialised W_eff and library GEMMs"),
     "VLMC_GELU": ("1", "0: torch's GELU kernel during the replay"),
+    "VLMC_GELU_MUL": ("1", "0: a gated FFN's gelu(wi_0(h)) * wi_1(h) runs as vlmc_gelu plus torch's mul over every row"),
     "VLMC_ATTN_FUSED": ("1", "0: an attention written op by op runs op by op"),
+    "VLMC_ATTN_PRE": ("1", "0: the qkv bias add and the q scale of an EVA attention run as torch's passes in front of vlmc_attn_fwd"),
     "VLMC_PAD_RAGGED": ("1", "0: ragged samples forwarded in groups of equal shape, never padded"),
     "VLMC_TOWER_PAD": ("1", "0: a finished tower runs one stacked pass per token count"),
     "VLMC_TOWER_SHARE_WIRING": ("1", "0: a finished tower is traced once per exact argument signature"),

@@ -49,7 +49,9 @@ ROUTES = {
     "attn_transposing_write": ({"VLMC_ATTN_TR": "0"}, "attn @ v with the operand transposed while writing LDS (no ds_read_b64_tr_b16)"),
     "lora_unfused": ({"VLMC_LORA_FUSED": "0"}, "SparseLoRA through a materialised W_eff, library GEMMs and a G = dY^T x in memory"),
     "gelu_torch": ({"VLMC_GELU": "0"}, "torch's GELU kernel (another instruction sequence in a tensor's last partial block)"),
+    "gelu_mul_two_ops": ({"VLMC_GELU_MUL": "0"}, "T5's gated product gelu(wi_0(h)) * wi_1(h) as vlmc_gelu plus torch's mul over every row instead of vlmc_gelu_mul over the real rows"),
     "attn_unfused": ({"VLMC_ATTN_FUSED": "0"}, "an attention written op by op runs op by op (vlmc_attn_matmul, torch elementwise, vlmc_softmax_rows) instead of vlmc_attn_fwd"),
+    "attn_operands_materialized": ({"VLMC_ATTN_PRE": "0"}, "the qkv bias add and the q scale of an EVA attention (eva_vit.py:133-141) run as torch's tensor passes in front of vlmc_attn_fwd instead of inside vlmc_attn_fwd_pre"),
     "replay_equal_shapes": ({"VLMC_PAD_RAGGED": "0", "VLMC_TOWER_PAD": "0"}, "ragged samples forwarded in groups of equal shape, never padded"),
     "dsnot_equal_shapes": ({"VLMC_DSNOT_PAD": "0"}, "DSnoT's walk forwards ragged samples in groups of equal shape (vlmc_act_moments, no per-sample token counts)"),
     "sparsegpt_padded_groups": ({"VLMC_SGPT_PAD": "1"}, "SparseGPT's walk forwards ragged samples as one padded group per block pass (vlmc_hessian_accum_rows over the group's row map)"),

@@ -37,7 +37,7 @@ _active = 0
 stats = {"kernel": 0, "library": 0, "grouped_launches": 0, "served_from_group": 0, "stash_dropped": 0, "attn_kernel": 0,
          "attn_library": 0, "mean_kernel": 0, "sdpa_kernel": 0, "sdpa_library": 0, "norm_kernel": 0, "softmax_kernel": 0,
          "attn_fused": 0, "attn_chain_unfused": 0, "attn_fused_checks": 0, "gelu_kernel": 0, "kernel_rows": 0, "attn_fused_lens": 0,
-         "kernel_slices": 0, "attn_fused_clamp": 0, "rope_kernel": 0, "rope_checks": 0}
+         "kernel_slices": 0, "attn_fused_clamp": 0, "rope_kernel": 0, "rope_checks": 0, "gelu_mul": 0, "gelu_mul_checks": 0, "attn_fused_pre": 0}
 
 # first member of a learned sibling group -> tuple of weak references to all members, in call order
 _SIBLINGS = weakref.WeakKeyDictionary()
@@ -284,6 +284,8 @@ class _Tracker:
         self.run, self.run_x, self.run_key = [], None, None      # consecutive calls on one tensor (the tensor kept alive)
         self.stash = {}                                          # id(module) -> (x, key, y)
         self.grouping = grouping_enabled()
+        self.tag_outputs = gelu_mul_enabled()
+        self.bias_fed = set()                                    # ids of the linears whose output is handed out as a `LazyOperand`
 
     def _close_run(self):
         if len(self.run) >= 2 and len({id(m) for m in self.run}) == len(self.run) and self.run[0] not in _SIBLINGS:
@@ -291,10 +293,13 @@ class _Tracker:
         self.run, self.run_x, self.run_key = [], None, None
 
     def call(self, mod, x):
-        if type(x) is LazyScores:
+        if type(x) in _LAZY_TYPES:
             x = x._realize()
         if not isinstance(x, torch.Tensor):
             return linear(x, mod.weight, mod.bias)
+        if id(mod) in self.bias_fed:                             # (a fused qkv linear: nobody's sibling)
+            y = self.single(mod, x)
+            return LazyOperand(y) if type(y) is torch.Tensor and y.dtype in ops._16BIT and y.is_cuda and not torch.is_grad_enabled() else y
         if not self.grouping:
             return self.single(mod, x)
         key = _input_key(x)
@@ -348,6 +353,11 @@ class _Tracker:
                             outs = ops.linear_fwd_group(xin, [g.weight for g in group], biases)
                         stats["kernel"] += len(group)
                         stats["grouped_launches"] += 1
+                        if self.tag_outputs:                     # (wi_0 / wi_1 of a gated FFN: `F.gelu` answers such a tensor lazily)
+                            for y in outs:
+                                y._vlmc_sibling = True
+                                if rm is not None:
+                                    y._vlmc_rows = rm
                         for g, y in zip(group[1:], outs[1:]):
                             self.stash[id(g)] = (x, key, y, mod)
                         return outs[0]
@@ -441,7 +451,7 @@ class LazyScores(torch.Tensor):
     def _realize(self):
         """The tensor the model's ops would have produced so far, on the unfused kernels."""
         if self._real is None:
-            t = ops.attn_matmul(self._q, self._kt)
+            t = ops.attn_matmul(_real_arg(self._q), _real_arg(self._kt))
             for func, args, kwargs in self._ops:
                 t = func(*[t if a_ is _SELF else a_ for a_ in args], **{k_: (t if v_ is _SELF else v_) for k_, v_ in kwargs.items()})
             self._real = t
@@ -472,16 +482,108 @@ def _lazy_dispatch(cls, func, types, args=(), kwargs=None):
 LazyScores.__torch_dispatch__ = classmethod(_lazy_dispatch)
 
 
+# ---- the gated product of T5 v1.1's feed-forward in ONE pass --------------------------------------------------------------------
+# `self.act(self.wi_0(h)) * self.wi_1(h)` (modeling_t5.py:337-341) is `vlmc_gelu` plus torch's `mul`: five passes over [rows, d_ff]
+# where three are needed, over the padding rows of a padded group too.  The patched `F.gelu` answers an output of a sibling-group
+# launch (wi_0 of the pair; `_Tracker` tags them, with the launch's row map) LAZILY: `LazyGelu` remembers the argument, and
+#   * `lazy * t` / `lazy.mul(t)` / `torch.mul(lazy, t)` with a plain tensor of the same shape and dtype runs `vlmc_gelu_mul` -- over
+#     the real rows only where the argument carries a row map (the padding rows of the product are zeros, as they were);
+#   * ANY other op first realizes it: `vlmc_gelu` on the argument, what the patched `F.gelu` returned before.
+# The first product of a signature (dtype, GELU form, row map?, 16-byte path?) is compared bit for bit with `ops.gelu(x) * y`, outside
+# graph capture; a mismatch keeps the two ops for good.  `VLMC_GELU_MUL=0`: never lazy.
+_GELU_MUL_OK = {}             # signature -> True / False
+
+
+def gelu_mul_enabled():
+    return config.flag("VLMC_GELU_MUL") and config.flag("VLMC_GELU")
+
+
+class LazyGelu(torch.Tensor):
+    """`F.gelu(x, approximate=...)` of a sibling-group output, not computed yet (see above)."""
+
+    @staticmethod
+    def __new__(cls, x, approximate):
+        r = torch.Tensor._make_wrapper_subclass(cls, x.shape, dtype=x.dtype, device=x.device)
+        r._x, r._approximate, r._real = x, approximate, None
+        return r
+
+    def _realize(self):
+        """What the patched `F.gelu` returns for a plain tensor."""
+        if self._real is None:
+            stats["gelu_kernel"] += 1
+            self._real = y = ops.gelu(self._x, self._approximate)
+            tag = getattr(self._x, "_vlmc_rows", None)
+            if tag is not None and y.shape == self._x.shape:
+                y._vlmc_rows = tag
+        return self._real
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        if func in _GELU_MUL_FUNCS:
+            r = _gelu_mul(args, kwargs)
+            if r is not NotImplemented:
+                return r
+        elif func in _LAZY_META_FUNCS or (getattr(func, "__name__", None) == "__get__" and
+                                         getattr(getattr(func, "__self__", None), "__name__", None) in _LAZY_META_PROPS):
+            with torch._C.DisableTorchFunctionSubclass():
+                return func(*args, **kwargs)
+        return func(*_real_args(args), **{k_: _real_arg(v_) for k_, v_ in kwargs.items()})
+
+
+LazyGelu.__torch_dispatch__ = classmethod(_lazy_dispatch)
+_LAZY_TYPES = (LazyScores, LazyGelu)       # (+ LazyOperand, below)
+_GELU_MUL_FUNCS = {torch.Tensor.__mul__, torch.Tensor.mul, torch.mul}
+
+
+def _gelu_mul(args, kw):
+    """`lazy * y` on `vlmc_gelu_mul`, or NotImplemented (the caller realizes the GELU and multiplies)."""
+    if kw or len(args) != 2:
+        return NotImplemented
+    a, y = args
+    if type(a) is not LazyGelu or a._real is not None or type(y) is not torch.Tensor or y.shape != a.shape or y.dtype != a.dtype or \
+            y.device != a.device or y.requires_grad or torch.is_grad_enabled():
+        return NotImplemented
+    x, approximate = a._x, a._approximate
+    rm = getattr(x, "_vlmc_rows", None)
+    if rm is not None and rm[0].shape[0] * x.shape[-1] != x.numel():
+        return NotImplemented
+    sig = (x.dtype, approximate, rm is not None, (x.data_ptr() | y.data_ptr()) % 16 == 0 and x.shape[-1] % 8 == 0)
+    ok = _GELU_MUL_OK.get(sig)
+    if ok is None:
+        if torch.cuda.is_current_stream_capturing():
+            return NotImplemented
+        fused = ops.gelu_mul(x, y, approximate, *(rm or ()))
+        ref = a._realize() * y
+        ok = _GELU_MUL_OK[sig] = bool(torch.equal(fused.view(torch.int16), ref.view(torch.int16)))
+        stats["gelu_mul_checks"] += 1
+        if not ok:
+            import warnings
+            warnings.warn(f"vlmc.forward: vlmc_gelu_mul does not reproduce gelu(x) * y for {sig}; this product stays two ops", RuntimeWarning)
+            return ref
+    elif not ok:
+        return NotImplemented
+    else:
+        fused = ops.gelu_mul(x, y, approximate, *(rm or ()))
+    stats["gelu_mul"] += 1
+    if rm is not None:
+        fused._vlmc_rows = rm
+    return fused
+
+
 def _realize_escaped():
     """Lazy products somebody still holds when the route goes down (they escaped the code that was to consume them): their
     values, now, on the kernels their records name.  (One whose chain reached a fused kernel is done.)"""
     for z in list(_LAZY_LIVE):
         if z._real is None and not z._consumed:
             z._realize()
+    for z in list(_OPERAND_LIVE):
+        if z._pending():
+            z._realize()
 
 
 def _real_arg(v):
-    if type(v) is LazyScores:
+    if type(v) in _LAZY_TYPES:
         return v._realize()
     if type(v) in (tuple, list):
         return type(v)(_real_arg(e) for e in v)
@@ -713,6 +815,209 @@ def _lazy_handlers():
 
 _LAZY_HANDLERS = _lazy_handlers()
 
+
+# ---- the output of a qkv linear that the model is about to bias, slice and scale ----------------------------------------------
+# `qkv = self.qkv(x) + cat(q_bias, 0, v_bias);  q, k, v = slices of its [B, N, 3, H, d] view;  q = q * scale` (eva_vit.py:133-141)
+# is a broadcast add over [B, N, 3 C] and a multiply over [B, H, N, d] that only hand the fused attention its operands.  A linear
+# flagged at setup (`_bias_fed_linears`: bias-free, its parent module owns 1-D parameters `q_bias` and `v_bias`) returns a
+# `LazyOperand`: the raw output, at most one pending addend (kept as an expanded, stride-0 view of the raw tensor's shape) and at most
+# one pending Python-scalar multiply after it.  View ops (`_OPERAND_VIEWS`) are applied to the raw tensor and to the addend's view
+# alike, so whatever slice reaches the matmul carries its own slice of the bias; the patched matmul hands raw views plus pre-ops to
+# `vlmc_attn_fwd_pre`.  ANY other function realizes the tensor -- torch's add and mul on the views, the model's own ops -- and goes on
+# with a plain tensor.  `VLMC_ATTN_PRE=0`: no linear is flagged.
+_OPERAND_LIVE = weakref.WeakSet()
+
+
+def attn_pre_enabled():
+    return config.flag("VLMC_ATTN_PRE") and attn_fused_enabled() and softmax_enabled()
+
+
+class LazyOperand(torch.Tensor):
+    @staticmethod
+    def __new__(cls, raw, add=None, mul=None):
+        r = torch.Tensor._make_wrapper_subclass(cls, raw.shape, strides=raw.stride(), dtype=raw.dtype, device=raw.device)   # (the layout the model's own tensor has)
+        r._raw, r._add, r._mul, r._real = raw, add, mul, None
+        _OPERAND_LIVE.add(r)
+        return r
+
+    def _realize(self):
+        """The tensor the model's ops would have produced: torch's add and mul, on the views."""
+        if self._real is None:
+            t = self._raw
+            if self._add is not None:
+                t = t + self._add
+            if self._mul is not None:
+                t = t * self._mul
+            self._real = t
+        return self._real
+
+    def _pending(self):
+        return self._real is None and (self._add is not None or self._mul is not None)
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        h = _OPERAND_HANDLERS.get(func)
+        if h is not None:
+            r = h(func, args, kwargs)
+            if r is not NotImplemented:
+                return r
+        elif func in _LAZY_META_FUNCS or (getattr(func, "__name__", None) == "__get__" and
+                                         getattr(getattr(func, "__self__", None), "__name__", None) in _LAZY_META_PROPS):
+            with torch._C.DisableTorchFunctionSubclass():
+                return func(*args, **kwargs)
+        return func(*_real_args(args), **{k_: _real_arg(v_) for k_, v_ in kwargs.items()})
+
+
+LazyOperand.__torch_dispatch__ = classmethod(_lazy_dispatch)
+_LAZY_TYPES = _LAZY_TYPES + (LazyOperand,)
+
+
+def _op_view(func, args, kw):
+    """A view op: applied to the raw tensor and to the addend's expanded view alike (a result that is no view of its input -- a
+    reshape that has to copy -- realizes instead)."""
+    a = args[0]
+    if type(a) is not LazyOperand or a._real is not None or any(type(v) in _LAZY_TYPES for v in args[1:]) or any(type(v) in _LAZY_TYPES for v in kw.values()):
+        return NotImplemented
+    with torch._C.DisableTorchFunctionSubclass():
+        raw = func(a._raw, *args[1:], **kw)
+        one = type(raw) is torch.Tensor
+        outs = (raw,) if one else tuple(raw)
+        if not outs or any(type(t) is not torch.Tensor or t._base is None or t.untyped_storage().data_ptr() != a._raw.untyped_storage().data_ptr() for t in outs):
+            return NotImplemented
+        adds = (None,) * len(outs)
+        if a._add is not None:
+            try:
+                ad = func(a._add, *args[1:], **kw)
+            except RuntimeError:
+                return NotImplemented
+            adds = (ad,) if one else tuple(ad)
+            if any(t.untyped_storage().data_ptr() != a._add.untyped_storage().data_ptr() or t.shape != r_.shape for t, r_ in zip(adds, outs)):
+                return NotImplemented
+    res = [LazyOperand(t, ad, a._mul) for t, ad in zip(outs, adds)]
+    return res[0] if one else type(raw)(res)
+
+
+def _op_reshape(func, args, kw):
+    """reshape / view: `view` for both (never a copy)"""
+    if kw or type(args[0]) is not LazyOperand:
+        return NotImplemented
+    shape = args[1] if len(args) == 2 and type(args[1]) in (tuple, list, torch.Size) else args[1:]
+    if not all(type(n) is int for n in shape):
+        return NotImplemented
+    try:
+        return _op_view(torch.Tensor.view, (args[0], *shape), {})
+    except RuntimeError:
+        return NotImplemented
+
+
+def _op_add(func, args, kw):
+    if kw or len(args) != 2:
+        return NotImplemented
+    a, b = args
+    if type(a) is not LazyOperand or a._real is not None or a._add is not None or a._mul is not None or type(b) is not torch.Tensor or \
+            b.dtype != a.dtype or b.device != a.device or b.requires_grad or torch.is_grad_enabled() or b.dim() > a.dim() or b.dim() == 0:
+        return NotImplemented
+    try:
+        view = b.expand(a._raw.shape)
+    except RuntimeError:
+        return NotImplemented
+    return LazyOperand(a._raw, view, None)
+
+
+def _op_mul(func, args, kw):
+    if kw or len(args) != 2:
+        return NotImplemented
+    a, c = args
+    if type(a) is not LazyOperand:
+        a, c = c, a                                                    # (number * lazy arrives as __rmul__(lazy, number) or mul(number, lazy))
+    if type(a) is not LazyOperand or a._real is not None or a._mul is not None or not _is_number(c) or torch.is_grad_enabled():
+        return NotImplemented
+    m = _fp32(c)                                                       # (torch multiplies a 16-bit tensor by a Python scalar in fp32)
+    if not (m == m and abs(m) != float("inf")):
+        return NotImplemented
+    return LazyOperand(a._raw, a._add, m)
+
+
+def _operand_handlers():
+    T = torch.Tensor
+    h = {f: _op_view for f in (T.permute, torch.permute, T.transpose, torch.transpose, T.__getitem__, T.select, torch.select, T.unbind,
+                               torch.unbind, T.narrow, torch.narrow, T.chunk, torch.chunk)}
+    h.update({T.reshape: _op_reshape, torch.reshape: _op_reshape, T.view: _op_reshape})
+    h.update({T.__add__: _op_add, T.add: _op_add, torch.add: _op_add, T.__mul__: _op_mul, T.__rmul__: _op_mul, T.mul: _op_mul, torch.mul: _op_mul})
+    return h
+
+
+_OPERAND_HANDLERS = _operand_handlers()
+
+
+def _bias_fed_linears(roots, patched):
+    """ids of the patched linears whose output the model biases itself: bias-free `nn.Linear` children of a module that owns 1-D
+    parameters `q_bias` and `v_bias` (the reference's eva_vit.Attention and the stand-in alike)."""
+    found, ok = set(), {id(m) for m in patched}
+    for root in roots:
+        for m in root.modules():
+            qb, vb = m._parameters.get("q_bias"), m._parameters.get("v_bias")
+            if qb is None or vb is None or qb.dim() != 1 or vb.dim() != 1:
+                continue
+            found |= {id(c) for c in m.children() if type(c) is nn.Linear and c.bias is None and id(c) in ok}
+    return found
+
+
+def _raw_of(t):
+    return t._raw if type(t) is LazyOperand else t
+
+
+def _head_addend(t):
+    """The pending addend of an operand [B, H, T, d] as the kernel takes it -- a [H, d] view, broadcast over batch and token, unit
+    stride along d -- or None when there is none; False when it is not of that form."""
+    ad = t._add if type(t) is LazyOperand else None
+    if ad is None:
+        return None
+    B, H, T, d = ad.shape
+    st = ad.stride()
+    if (B > 1 and st[0] != 0) or (T > 1 and st[2] != 0) or (d > 1 and st[3] != 1) or st[1] < 0 or ad.data_ptr() % 2:
+        return False
+    return ad[0, :, 0, :]
+
+
+def _pre_ops(q, k, v):
+    """(raw q, raw k, raw v, keyword arguments of `ops.attn_fused`) for operands of which at least one is a `LazyOperand` with pending
+    ops the kernel applies itself; None when it does not (the caller realizes them)."""
+    if not any(type(t) is LazyOperand and t._pending() for t in (q, k, v)) or any(type(t) is LazyOperand and t._real is not None for t in (q, k, v)):
+        return None
+    if any(type(t) is LazyOperand and t._mul is not None for t in (k, v)):
+        return None
+    adds = [_head_addend(t) for t in (q, k, v)]
+    if any(ad is False for ad in adds):
+        return None
+    kw = {name: ad for name, ad in zip(("q_add", "k_add", "v_add"), adds) if ad is not None}
+    if type(q) is LazyOperand and q._mul is not None:
+        kw["q_mul"] = q._mul
+    return _raw_of(q), _raw_of(k), _raw_of(v), kw
+
+
+def _pre_trial_ok(q, k, v, mul, adds, plan, kw):
+    """The first-use comparison once more on SEEDED, NON-TRIVIAL addends (a model whose biases are all zeros would not show a wrong
+    add): the kernel's pre-ops against `ops.attn_fused` on operands materialized by torch."""
+    g = torch.Generator(device=q.device).manual_seed(20250611)
+    H, d = q.shape[1], q.shape[3]
+    trial = {name: (torch.randn(H, d, generator=g, device=q.device) * 0.75).to(q.dtype) for name in ("q_add", "k_add", "v_add") if name in kw}
+    if "k_add" in trial:
+        trial["k_add"][0].zero_()                                      # (one head adds the zeros the EVA chain hands K)
+    tk = dict(kw, **trial)
+    mat = []
+    for t, name in ((q, "q_add"), (k, "k_add"), (v, "v_add")):
+        if name in trial:
+            t = t + trial[name][None, :, None, :]
+        if name == "q_add" and "q_mul" in kw:
+            t = t * kw["q_mul"]
+        mat.append(t)
+    got = ops.attn_fused(q, k, v, mul, adds, plan, **tk)
+    want = ops.attn_fused(mat[0], mat[1], mat[2], mul, adds)
+    return bool(torch.equal(got.contiguous().view(torch.int16), want.contiguous().view(torch.int16)))
+
+
 def _chain_signature(a, v):
     q = a._q
 
@@ -723,11 +1028,30 @@ def _chain_signature(a, v):
             tuple(f is _SELF or getattr(f, "__name__", "") for f, _a, _k in a._ops), a._clamp is not None)
 
 
+def _settle_operands(a, b):
+    """The operands of a lazy chain for the fused kernel: (v, pre) with `pre` = (raw q, raw k, raw v, pre-op keywords) when the
+    kernel applies their pending ops itself, else None with every `LazyOperand` among them realized."""
+    if type(a._q) is not LazyOperand and type(a._kt) is not LazyOperand and type(b) is not LazyOperand:
+        return b, None
+    pre = None
+    if a._real is None and a._clamp is None and len(a._adds) <= 1 and not torch.is_grad_enabled():
+        pre = _pre_ops(a._q, a._kt.transpose(-1, -2), b)
+    if pre is None:
+        a._q, a._kt, b = _real_arg(a._q), _real_arg(a._kt), _real_arg(b)
+    return b, pre
+
+
 def _lazy_matmul(a, b, matmul):
     """`matmul(lazy, v)`: the fused kernel when the recorded chain is one it computes (and has reproduced the unfused bits once),
     else the realized tensor times v."""
-    fusable = a._real is None and type(b) is torch.Tensor and attn_fused_enabled() and not torch.is_grad_enabled() and \
+    b, pre = _settle_operands(a, b)
+    fusable = a._real is None and type(b) in (torch.Tensor, LazyOperand) and attn_fused_enabled() and not torch.is_grad_enabled() and \
         (a._state == "p16" or (a._state == "p32" and torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() == a._dt16))
+    if fusable and pre is not None:
+        r = _lazy_matmul_pre(a, b, matmul, pre)
+        if r is not None:
+            return r
+        a._q, a._kt, b = _real_arg(a._q), _real_arg(a._kt), _real_arg(b)
     if fusable:
         k = a._kt.transpose(-1, -2)
         plan = ops.attn_fused_plan(a._q, k, b, a._adds)
@@ -762,7 +1086,43 @@ def _lazy_matmul(a, b, matmul):
                     stats["attn_fused_lens"] += 1
                     return ops.attn_fused(a._q, k, b, a._mul, a._adds, plan, ql, kl)
                 return ops.attn_fused(a._q, k, b, a._mul, a._adds, plan)
-    return matmul(a._realize(), b)
+    return matmul(a._realize(), _real_arg(b))
+
+
+def _lazy_matmul_pre(a, v, matmul, pre):
+    """`_lazy_matmul` for operands with pending ops: `vlmc_attn_fwd_pre` on the raw views once its signature -- the chain's, extended by
+    which pre-ops are present -- has reproduced the unfused sequence bit for bit, on the model's own values and on seeded trial addends;
+    None: the caller realizes the operands and goes on as before."""
+    q, k, vr, kw = pre
+    plan = ops.attn_fused_plan(q, k, vr, a._adds)
+    if plan is None:
+        return None
+    sig = _chain_signature(a, v) + (tuple(sorted(kw)),)
+    ok = _FUSED_OK.get(sig)
+    ql, kl = _pad_lengths(q, k, a._adds) if _PAD_LENGTHS is not None else (None, None)
+    if ok is None:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        fused = ops.attn_fused(q, k, vr, a._mul, a._adds, plan, **kw)
+        ref = matmul(a._realize(), _real_arg(v))
+        ok = bool(fused.shape == ref.shape and torch.equal(fused.contiguous().view(torch.int16), ref.contiguous().view(torch.int16)))
+        ok = _FUSED_OK[sig] = ok and _pre_trial_ok(q, k, vr, a._mul, a._adds, plan, kw)
+        stats["attn_fused_checks"] += 1
+        if not ok:
+            import warnings
+            warnings.warn(f"vlmc.forward: the fused attention with operand pre-ops does not reproduce the unfused op sequence for {sig}; "
+                          "this chain keeps its operands materialized", RuntimeWarning)
+            return ref
+    elif not ok:
+        return None
+    else:
+        lens = {} if ql is None and kl is None else {"q_len": ql, "k_len": kl}
+        fused = ops.attn_fused(q, k, vr, a._mul, a._adds, plan, **lens, **kw)
+        stats["attn_fused_lens"] += bool(lens)
+    stats["attn_fused"] += 1
+    stats["attn_fused_pre"] += 1
+    a._consumed = True
+    return fused
 
 
 def _make_matmul(orig):
@@ -779,6 +1139,14 @@ def _make_matmul(orig):
             return _lazy_matmul(a, b, matmul)
         if type(b) is LazyScores:
             return orig(a, b._realize(), *args, **kw)
+        if type(a) is LazyOperand or type(b) is LazyOperand:
+            ra, rb = _raw_of(a), _raw_of(b)
+            if lazy and not args and not kw and not torch.is_grad_enabled() and ra.dim() == 4 and rb.dim() == 4 and rb.stride(2) == 1 and \
+                    ra.stride(3) == 1 and rb.shape[3] > 1 and ra.dtype is rb.dtype and ra.shape[:2] == rb.shape[:2] and \
+                    not (torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() != ra.dtype) and \
+                    ops.attn_fused_plan(ra, rb.transpose(2, 3), rb.transpose(2, 3)) is not None:
+                return LazyScores(a, b, (*ra.shape[:3], rb.shape[3]), ra.dtype)       # (q @ k^T on operands with pending ops: settled at attn @ v)
+            return matmul(_real_arg(a), _real_arg(b), *args, **kw)
         if not args and not kw and type(a) is Tensor and type(b) is Tensor and a.dim() >= 3 and not torch.is_grad_enabled():
             if (torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() != a.dtype) or (a.dtype is f32 and not f32_on):
                 return orig(a, b)                                   # (autocast would cast the operands: the library's call)
@@ -877,12 +1245,15 @@ def _make_gelu(orig):
     which bits a sample's last rows get depends on how many samples share the forward -- the one elementwise op of the blocks that is
     not batch-invariant in torch.  The kernel uses the body's arithmetic for every element (`VLMC_GELU=0`: torch's)."""
     Tensor = torch.Tensor
+    lazy = gelu_mul_enabled()
 
     def gelu(x, *args, **kw):
         if _ident() == _mm_owner:
             if type(x) is Tensor and x.is_cuda and (x.dtype in ops._16BIT or (x.dtype is torch.float32 and not torch.is_autocast_enabled() and f32_enabled())) and \
                     not torch.is_grad_enabled() and not args and \
                     not (set(kw) - {"approximate"}) and kw.get("approximate", "none") in ("none", "tanh") and x.numel() > 0:
+                if lazy and x.dtype is not torch.float32 and getattr(x, "_vlmc_sibling", False):
+                    return LazyGelu(x, kw.get("approximate", "none"))          # (the gated product: computed where it is multiplied)
                 stats["gelu_kernel"] += 1
                 y = ops.gelu(x, kw.get("approximate", "none"))
                 tag = getattr(x, "_vlmc_rows", None)
@@ -1184,6 +1555,8 @@ def invariant_linears(modules, roots=()):
         return
     patched = [m for m in modules if type(m) is nn.Linear and "forward" not in m.__dict__]
     tracker = _Tracker(patched)
+    if roots and attn_pre_enabled() and attn_matmul_enabled():
+        tracker.bias_fed = _bias_fed_linears(roots, patched)
     for m in patched:
         m.forward = (lambda mod: (lambda x: tracker.call(mod, x)))(m)
     _active += 1

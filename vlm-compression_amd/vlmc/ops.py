@@ -451,6 +451,27 @@ def gelu(x: torch.Tensor, approximate: str = "none") -> torch.Tensor:
     return y
 
 
+def gelu_mul(x: torch.Tensor, y: torch.Tensor, approximate: str = "none", rowmap=None, n_real: int = 0) -> torch.Tensor:
+    """`F.gelu(x, approximate=...) * y` for 16-bit CUDA tensors of one shape in one pass, with the bits of `gelu(x) * y` (include/vlmc.h:
+    vlmc_gelu_mul): T5 v1.1's gated product.  x and y are read in place where their rows [.., cols] have one pitch (column slices of one
+    buffer, tensors of their own).  `rowmap` / `n_real` (what `linear_fwd_rows` took): only rows `rowmap[:n_real]` of the flattened
+    operands are read and computed, rows `rowmap[n_real:]` of the result are zeros."""
+    _need_gpu(x, y, rowmap)
+    if x.dtype not in _16BIT or y.dtype != x.dtype or x.shape != y.shape or x.dim() < 1 or approximate not in ("none", "tanh"):
+        raise TypeError("vlmc.gelu_mul: fp16 / bf16 tensors of one dtype and shape and approximate 'none' or 'tanh' expected")
+    out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    cols = x.shape[-1]
+    if out.numel() == 0:
+        return out
+    x2, rows, ldx = _rows(x, cols)
+    y2, _, ldy = _rows(y, cols)
+    if rowmap is not None and not (_rowmap_ok(rowmap, n_real, rows) or (n_real == 0 and _rowmap_ok(rowmap, 1, rows))):
+        raise ValueError("vlmc.gelu_mul: rowmap a contiguous int32 [rows of x] tensor and 0 <= n_real <= rows expected")
+    _lib.check(_lib.load().vlmc_gelu_mul(x2.data_ptr(), y2.data_ptr(), out.data_ptr(), _DT[x.dtype], 1 if approximate == "tanh" else 0, rows, cols,
+                                         ldx, ldy, cols, rowmap.data_ptr() if rowmap is not None else None, int(n_real), _stream()))
+    return out
+
+
 def softmax_rows(x: torch.Tensor, out_dtype=None) -> torch.Tensor:
     """`torch.softmax(x, -1[, dtype=out_dtype])` on the padding-invariant kernel (include/vlmc.h: vlmc_softmax_rows): fp32 -> fp32,
     fp16 / bf16 -> the same dtype (fp32 arithmetic, one rounding) or fp32."""
@@ -512,15 +533,23 @@ def _add_strides(t, B, H, Tq):
     return _I64x4(*(0 if n == 1 else s for n, s in zip(sh[:3], st[:3])), max(1, st[3]))
 
 
-def attn_fused(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mul=None, adds=(), _plan=None, q_len=None, k_len=None) -> torch.Tensor:
+def attn_fused(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mul=None, adds=(), _plan=None, q_len=None, k_len=None, *, q_add=None,
+               k_add=None, v_add=None, q_mul=None) -> torch.Tensor:
     """The reference-op attention chain in one launch (include/vlmc.h: vlmc_attn_fwd):
         s = q @ k^T;  [s = s * mul];  [s = s + adds[0] [+ adds[1]]];  p = softmax in fp32, rounded;  out = p @ v
     every intermediate rounded to the dtype where the tensor op would round it -- the bits of the unfused sequence on
     `attn_matmul`, torch's elementwise ops and `softmax_rows`.  Returns [B, H, Tq, d] as a VIEW of a contiguous [B, Tq, H, d]
     tensor (the model's `.transpose(1, 2).reshape(B, Tq, H * d)` is free).  `mul`: a Python float already rounded to fp32.
     `q_len` / `k_len` (int32 device tensors [B], a padded group of ragged samples): output rows behind q_len[b] are zeros; keys
-    behind k_len[b] -- which an addend must mask -- are skipped (include/vlmc.h: vlmc_attn_fwd_lens)."""
-    return _attn_fused(q, k, v, mul, adds, _plan, q_len, k_len, None)
+    behind k_len[b] -- which an addend must mask -- are skipped (include/vlmc.h: vlmc_attn_fwd_lens).
+    Operand pre-ops (keywords; include/vlmc.h: vlmc_attn_fwd_pre): `q_add` / `k_add` / `v_add`, 16-bit [H, d] tensors with unit stride
+    along d (slices of the model's qkv bias), are added to every token's row of their operand, `q_mul` (a Python float already rounded
+    to fp32) then multiplies q -- each step rounded to the dtype like `qkv + bias` and `q * scale` (eva_vit.py:133-141), so q, k and v
+    may be the raw slices of the qkv linear's output.  At most one entry in `adds` then."""
+    pre = None
+    if q_add is not None or k_add is not None or v_add is not None or q_mul is not None:
+        pre = (q_add, k_add, v_add, q_mul)
+    return _attn_fused(q, k, v, mul, adds, _plan, q_len, k_len, None, pre)
 
 
 def attn_fused_clamp(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mul=None, adds=(), clamp_min: float = 0.0, _plan=None, q_len=None,
@@ -533,8 +562,8 @@ def attn_fused_clamp(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mul=None
     return _attn_fused(q, k, v, mul, adds, _plan, q_len, k_len, float(clamp_min))
 
 
-def _attn_fused(q, k, v, mul, adds, _plan, q_len, k_len, clamp_min):
-    _need_gpu(q, k, v, q_len, k_len)
+def _attn_fused(q, k, v, mul, adds, _plan, q_len, k_len, clamp_min, pre=None):
+    _need_gpu(q, k, v, q_len, k_len, *(pre[:3] if pre else ()))
     plan = _plan if _plan is not None else attn_fused_plan(q, k, v, adds)
     if plan is None:
         raise TypeError("vlmc.attn_fused: q [B, H, Tq, d], k, v [B, H, Tk, d] of one 16-bit dtype with unit stride along d, at most "
@@ -553,7 +582,17 @@ def _attn_fused(q, k, v, mul, adds, _plan, q_len, k_len, clamp_min):
             None if a0 is None else a0.data_ptr(), None if a0 is None else _add_strides(a0, B, H, Tq),
             None if a1 is None else a1.data_ptr(), None if a1 is None else _add_strides(a1, B, H, Tq))
     lens = (None if q_len is None else q_len.data_ptr(), None if k_len is None else k_len.data_ptr(), _stream())
-    if clamp_min is None:
+    if pre is not None:
+        H = q.shape[1]
+        for t in pre[:3]:
+            if t is not None and (t.dtype != q.dtype or t.device != q.device or t.shape != (H, d) or (t.stride(1) != 1 and d != 1) or t.stride(0) < 0):
+                raise TypeError("vlmc.attn_fused: q_add / k_add / v_add must be [heads, head_dim] tensors of the operands' dtype with unit stride along head_dim")
+        if len(adds) > 1:
+            raise ValueError("vlmc.attn_fused: at most one score addend with operand pre-ops")
+        ptrs = [x for t in pre[:3] for x in ((None, 0) if t is None else (t.data_ptr(), 0 if H == 1 else t.stride(0)))]
+        _lib.check(_lib.load().vlmc_attn_fwd_pre(*head, 0, 0.0, *lens[:2], *ptrs, 0 if pre[3] is None else 1, 0.0 if pre[3] is None else float(pre[3]),
+                                                 lens[2]))
+    elif clamp_min is None:
         _lib.check(_lib.load().vlmc_attn_fwd_lens(*head, *lens))
     else:
         _lib.check(_lib.load().vlmc_attn_fwd_clamp(*head, clamp_min, *lens))
