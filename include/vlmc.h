@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VLMC_ABI_VERSION 28
+#define VLMC_ABI_VERSION 29
 
 #define VLMC_OK 0
 #define VLMC_EINVAL (-1)     /* bad argument (shape, dtype, alignment, null pointer) */
@@ -322,6 +322,20 @@ size_t vlmc_linear_fwd_bm_workspace(int64_t M, int64_t N, int64_t K);
 int vlmc_linear_fwd_bm(const void *X, const void *values, const uint8_t *meta, const uint16_t *offs, const int64_t *rowptr, int64_t nnz,
                        const void *bias, int dtype, int64_t M, int64_t N, int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace,
                        size_t workspace_bytes, void *stream);
+/* The linear above at ANY M >= 1 with NO workspace (prefill, the vision tower: the dense zero-filled forward of a model under an
+ * unstructured mask, wanda_pruner.py:330-339, train.py:626-637, :677-714, computed from the packed bytes): the tiled GEMM behind
+ * vlmc_linear_fwd with its weight operand bitmap-packed -- a workgroup's threads find each 8-column chunk's values through rowptr,
+ * offs and the popcount of its step's meta bytes (fetched one K-tile ahead of the values), load them as five aligned dwords and
+ * expand them on the way into LDS, so no dense copy exists anywhere.  Bit for bit vlmc_linear_fwd on vlmc_unpack_bm of the same
+ * buffers, in every tile shape (the shape is picked as vlmc_linear_fwd picks it).  Arguments as vlmc_linear_fwd_bm without the
+ * workspace, the same refusals, every one before the device is touched; meta, offs and rowptr are TRUSTED as above and the index into
+ * values is clamped to [0, nnz] all the same.
+ * vlmc_linear_fwd_bm_tiled_max_rows(): the largest M for which this kernel measured faster than unpacking into a workspace (a
+ * build-time constant chosen from tools/bench_linear24.py --tiled --format bm; 0 = at no M, else >= vlmc_linear_fwd_bm_max_rows()):
+ * advice for callers that route by M, as vlmc.ops does -- the entry point itself takes any M.                                     */
+int vlmc_linear_fwd_bm_tiled_max_rows(void);
+int vlmc_linear_fwd_bm_tiled(const void *X, const void *values, const uint8_t *meta, const uint16_t *offs, const int64_t *rowptr, int64_t nnz,
+                             const void *bias, int dtype, int64_t M, int64_t N, int64_t K, int64_t ldx, void *Y, int64_t ldy, void *stream);
 
 /* ---- dense calibration forward of one linear (MFMA) ---------------------------------------------
  * Replaces `F.linear(x, weight, bias)` inside the block forwards of the calibration replay,

@@ -13,13 +13,16 @@ Every row is measured `--repeats` times with the routes alternating; the table p
 
     python tools/bench_linear24.py [--format 24|48|bm] [--density 0.5] [--only v7b] [--rows 1,8,16] [--repeats 3] [--out profiles/linear24.md]
 
-`--tiled` (formats 24 and 48): the PREFILL sizes instead -- for every shape above plus the four ViT-g linears and every row count of the
+`--tiled` (every format; `--format bm` with `--density`): the PREFILL sizes instead -- for every shape above plus the four ViT-g linears and every row count of the
 ladder 65 .. 4096, on the graph clock, alternating: (a) the unpack route (unpack into scratch + dense kernel: what runs above
-`vlmc_linear_fwd_24_tiled_max_rows()`), (b) the tiled kernel that takes the weight packed (vlmc_linear_fwd_24_tiled / _48_tiled), (c) the
+`vlmc_linear_fwd_24_tiled_max_rows()` / `vlmc_linear_fwd_bm_tiled_max_rows()`), (b) the tiled kernel that takes the weight packed
+(vlmc_linear_fwd_24_tiled / _48_tiled / _bm_tiled), (c) the
 dense kernel on an unpacked weight that already exists (the floor, for orientation).  (a) and (b) are compared bit for bit before
 anything is timed.  The last lines give, per row count, whether (b) beats (a) by more than the larger spread on EVERY shape, and the
-largest ladder value up to which it does: the rule VLMC_LINEAR_NM_TILED_MAX_ROWS is set by (profiles/linear_nm_tiled.md).
+largest ladder value up to which it does: the rule VLMC_LINEAR_NM_TILED_MAX_ROWS (profiles/linear_nm_tiled.md) and
+VLMC_LINEARBM_TILED_MAX_ROWS (profiles/linearbm_tiled.md) are set by.
     python tools/bench_linear24.py --tiled --format 24 --out <file>;  python tools/bench_linear24.py --tiled --format 48 --out <file>
+    python tools/bench_linear24.py --tiled --format bm [--density 0.5] --out <file>
 (`--format 48 --rows 1,2,4,8,16,32,48,64,128 --out <file>` gives the table of profiles/linear48.md; `--format bm --out <file>` that of
 profiles/linearbm.md, measured on a build whose VLMC_LINEARBM_MAX_ROWS is 64 so that the packed kernel is timed at every candidate limit)"""
 import argparse
@@ -93,11 +96,11 @@ def med_spread(v):
 
 def tiled_main(args):
     """--tiled: the unpack route, the tiled packed kernel and the dense kernel at the prefill row counts"""
-    assert args.format in ("24", "48"), "--tiled: the two n:m formats"
     n_keep, n_of = (2, 4) if args.format == "24" else (4, 8)
     pack, packed_fwd = getattr(ops, "pack_" + args.format), getattr(ops, "linear_fwd_" + args.format)
     rows = [int(r) for r in args.rows.split(",")] if args.rows else list(LADDER)
-    lines = [f"format {n_keep}:{n_of} (`vlmc_linear_fwd_{args.format}_tiled`); fp16; cold weights; graph clock, us per call; median of {args.repeats} "
+    what = f"unstructured, {args.density:g} of every row kept" if args.format == "bm" else f"{n_keep}:{n_of}"
+    lines = [f"format {what} (`vlmc_linear_fwd_{args.format}_tiled`); fp16; cold weights; graph clock, us per call; median of {args.repeats} "
              "(spread = max - min); tiled wins = its median is below the unpack route's by more than the larger of the two spreads",
              "",
              "| shape (N x K) | M | (a) unpack route us (spread) | (b) tiled us (spread) | (c) dense us (spread) | (b) / (a) | (b) / (c) | tiled wins |",
@@ -110,7 +113,10 @@ def tiled_main(args):
         g = torch.Generator(device=DEV).manual_seed(0)
         W = (torch.randn(N, K, device=DEV, generator=g) * 0.02).half()
         sq = torch.rand(K, device=DEV, generator=g) + 0.5
-        keep, _ = ops.wanda_select(W, sq, "nm", n=n_keep, m=n_of)
+        if args.format == "bm":
+            keep, _ = ops.wanda_select(W, sq, "row", k=K - int(round(K * args.density)))
+        else:
+            keep, _ = ops.wanda_select(W, sq, "nm", n=n_keep, m=n_of)
         packed = pack(W, keep)
         W = getattr(ops, "unpack_" + args.format)(*packed, want_mask=False)[0]      # the weight the packed bytes stand for
         packed_bytes = sum(t.numel() * t.element_size() for t in packed)
@@ -161,7 +167,7 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--format", default="24", choices=("24", "48", "bm"), help="the packed format: 2:4 selectors, 4:8 bit masks or the bitmap of any mask")
     ap.add_argument("--density", type=float, default=0.5, help="--format bm: the share of every row's columns that is kept")
-    ap.add_argument("--tiled", action="store_true", help="formats 24 / 48: the unpack route, the tiled packed kernel and the dense kernel at the "
+    ap.add_argument("--tiled", action="store_true", help="the unpack route, the tiled packed kernel and the dense kernel at the "
                     "prefill row counts " + ",".join(map(str, LADDER)))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_linear24.py measures on the GPU only"

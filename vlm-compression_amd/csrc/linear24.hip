@@ -27,13 +27,14 @@
 // M > vlmc_linear_fwd_24_max_rows() (prefill, the vision tower): compute-bound, so the entry point unpacks into the caller's
 // workspace (unpack24_kernel / unpack48_kernel) and runs the dense launch -- the same bits by construction.  The entry points
 // vlmc_linear_fwd_24_tiled / _48_tiled take any M without a workspace: the tiled GEMM of gemm_nt.hip with the weight operand packed
-// (expanded between the global load and the LDS store), again the same bits.
+// (expanded between the global load and the LDS store), again the same bits; vlmc_linear_fwd_bm_tiled does the same for the bitmap format.
 //
 // The third format is the bitmap format of packbm.hip (ANY mask: values [nnz + 16], meta [N, K / 8], offs [N, ceil(K / 32)],
 // rowptr [N + 1]), entry point vlmc_linear_fwd_bm with a row limit of its own: the same kernel, chain, carry tiles and epilogue; its
 // expansion policy ExpandBM brings its own loads (a chunk is 0 to 8 halfwords at an arbitrary 2-byte offset whose address comes from
 // the metadata, which is therefore fetched one batch further ahead than the values) and its own batch registers.
 #include "common.hpp"
+#include "expand_bm.hpp"
 #include "expand_nm.hpp"
 #include "mfma.hpp"
 
@@ -56,6 +57,13 @@ static_assert(VLMC_LINEARBM_MAX_ROWS % 16 == 0 && VLMC_LINEARBM_MAX_ROWS >= 16 &
 #endif
 static_assert(VLMC_LINEAR_NM_TILED_MAX_ROWS == 0 || VLMC_LINEAR_NM_TILED_MAX_ROWS >= VLMC_LINEAR24_MAX_ROWS, "0 (never) or at least the packed kernel's own limit");
 
+// the same for the bitmap format (gemm_nt_kernel<.., PackedBM>) above VLMC_LINEARBM_MAX_ROWS: chosen from tools/bench_linear24.py --tiled
+// --format bm (profiles/linearbm_tiled.md); 0 = never, else >= that limit
+#ifndef VLMC_LINEARBM_TILED_MAX_ROWS
+#define VLMC_LINEARBM_TILED_MAX_ROWS 0
+#endif
+static_assert(VLMC_LINEARBM_TILED_MAX_ROWS == 0 || VLMC_LINEARBM_TILED_MAX_ROWS >= VLMC_LINEARBM_MAX_ROWS, "0 (never) or at least the packed kernel's own limit");
+
 namespace vlmc {
 
 constexpr int L24_WAVES = 16;
@@ -63,6 +71,11 @@ constexpr int L24_WAVES = 16;
 // gemm_nt.hip: the register-staged tiled GEMM with the weight operand packed n:m (fmt 24 or 48), arguments checked here
 int linear_nm_tiled_launch(const char *fn, int fmt, const void *X, const void *values, const uint8_t *meta, const void *bias, int dtype,
                            int64_t M, int64_t N, int64_t K, int64_t ldx, void *Y, int64_t ldy, void *stream);
+
+// gemm_nt.hip: the same kernel with the weight operand bitmap-packed, arguments checked here
+int linear_bm_tiled_launch(const char *fn, const void *X, const void *values, const uint8_t *meta, const uint16_t *offs, const int64_t *rowptr,
+                           int64_t nnz, const void *bias, int dtype, int64_t M, int64_t N, int64_t K, int64_t ldx, void *Y, int64_t ldy,
+                           void *stream);
 
 struct Linear24Args {
     const uint16_t *X;            // [M, K], row stride ldx
@@ -136,78 +149,21 @@ struct Expand48 : ExpandNM {
 };
 static_assert(64 * L24_WAVES == 256 * 4, "Expand48 / ExpandBM::init: one thread per selector dword (fill_perm_table<1024>)");
 
-// bm: the byte means what the 4:8 byte means, with 0 to 8 bits set.  The chunk's values are the 0 to 8 halfwords from index
-//     i = min(rowptr[n] + offs[n][s] + popcount(the step's meta bytes before this quarter), nnz)
-// of `values`, fetched as the FIVE ALIGNED dwords from i >> 1 (one 16-byte load that needs 4-byte alignment only, one dword) and
-// shifted down by the odd halfword with v_alignbyte_b32 -- halfwords i & ~1 .. (i & ~1) + 9 <= nnz + 9, inside the 16 of tail
-// whatever the metadata holds.  The step's four meta bytes sit at byte wrow * K / 8 + 4 s of `meta`, at any alignment: the two
-// aligned dwords round it, the second clamped to the last dword that holds a byte of meta (its bytes are then other chunks' or
-// none's: only the bytes of chunks < K / 8 of this row are ever used).
-// Expansion: value r of the chunk is halfword r of the four shifted dwords {v0 .. v3}; output dword j is
-// perm({v1, v0}, A[byte][j]) | perm({v3, v2}, B[byte][j]) with A the selectors of values 0..3 (the 4:8 table) and B those of values
-// 4..7, 0x0c for "not from this pair": 8 KiB of LDS.
-// The address of the values depends on meta and offs, so those are fetched ONE BATCH FURTHER AHEAD (`prime`): when a wave hands on
-// and issues its next batch's value loads, that batch's metadata arrived a whole round ago, and the metadata of the batch after
-// goes out with them.
-typedef uint32_t u32x4_a4_t __attribute__((ext_vector_type(4), aligned(4)));
-struct ExpandBM {
+// bm (expand_bm.hpp: the index lookup, the five-dword load, the shift and the two selector tables): a chunk is 0 to 8 halfwords at an
+// arbitrary 2-byte offset whose address depends on meta and offs, so those are fetched ONE BATCH FURTHER AHEAD (`prime`): when a wave
+// hands on and issues its next batch's value loads, that batch's metadata arrived a whole round ago, and the metadata of the batch
+// after goes out with them.
+struct ExpandBM : BMRow {
     using Args = LinearBMArgs;
     template <int MT> static constexpr int steps() { return MT <= 2 ? 4 : 2; }
-    template <int D> struct Regs {
-        u32x4_t v[D];                          // the aligned dwords 0..3 from i >> 1, v4: the fifth
-        uint32_t v4[D], code[D];               // code: the chunk's byte | (i & 1) << 8
-        uint32_t mlo[D], mhi[D], off[D];       // primed: the two aligned dwords round the step's meta bytes, offs[n][s]
-    };
-    const u32x4_t *sel;                        // [0, 256): A, [256, 512): B
-    const uint32_t *val32, *meta32;
-    const uint16_t *orow;
-    int64_t rp, nnz, mbyte, last_dw;
-    int chunks;
-    uint32_t q8;
+    template <int D> using Regs = BMRegs<D>;
     static __device__ __forceinline__ const uint16_t *spare(const Args &a) { return a.offs; }
     __device__ __forceinline__ void init(int tid) {
         __shared__ u32x4_t table[512];
-        fill_perm_table<64 * L24_WAVES, 0>(reinterpret_cast<uint32_t *>(table), tid);
-        fill_perm_table<64 * L24_WAVES, 4>(reinterpret_cast<uint32_t *>(table) + 1024, tid);
+        fill_bm_tables<64 * L24_WAVES>(table, tid);
         sel = table;
     }
-    __device__ __forceinline__ void row(const Args &a, int wrow, int fq) {
-        chunks = a.K >> 3;
-        val32 = reinterpret_cast<const uint32_t *>(a.values), meta32 = reinterpret_cast<const uint32_t *>(a.meta);
-        orow = a.offs + int64_t(wrow) * ((chunks + 3) >> 2);
-        rp = a.rowptr[wrow], nnz = a.nnz;
-        mbyte = int64_t(wrow) * chunks, last_dw = (int64_t(a.N) * chunks - 1) >> 2;
-        q8 = 8u * uint32_t(fq);
-    }
-    template <int D> __device__ __forceinline__ void prime(Regs<D> &R, int d, int cc) const {
-        const int s = cc >> 2;
-        const int64_t w = (mbyte + 4 * s) >> 2;                       // (chunk 4 s of this row exists: w <= last_dw)
-        R.mlo[d] = meta32[w];
-        R.mhi[d] = meta32[min(w + 1, last_dw)];
-        R.off[d] = orow[s];
-    }
-    template <int D> __device__ __forceinline__ void load(Regs<D> &R, int d, int cc, int ahead) const {
-        const int s = cc >> 2;                                        // (a clamped chunk keeps this lane's quarter: any valid address)
-        const uint32_t m = __builtin_amdgcn_alignbyte(R.mhi[d], R.mlo[d], uint32_t(mbyte + 4 * s) & 3u);
-        const uint32_t before = uint32_t(__popc(m & ((1u << q8) - 1u)));
-        const int64_t i = max(min(rp + int64_t(R.off[d] + before), nnz), int64_t(0));
-        R.code[d] = ((m >> q8) & 0xffu) | uint32_t(i & 1) << 8;
-        const uint32_t *p = val32 + (i >> 1);
-        R.v[d] = *reinterpret_cast<const u32x4_a4_t *>(p);
-        R.v4[d] = p[4];
-        prime(R, d, ahead);
-    }
-    template <int D> __device__ __forceinline__ u32x4_t expand(const Regs<D> &R, int d) const {
-        const uint32_t code = R.code[d], sh = (code >> 8) << 1;       // 0 or 2 bytes
-        const u32x4_t r = R.v[d];
-        const uint32_t v0 = __builtin_amdgcn_alignbyte(r[1], r[0], sh), v1 = __builtin_amdgcn_alignbyte(r[2], r[1], sh),
-                       v2 = __builtin_amdgcn_alignbyte(r[3], r[2], sh), v3 = __builtin_amdgcn_alignbyte(R.v4[d], r[3], sh);
-        const u32x4_t sa = sel[code & 0xffu], sb = sel[256u + (code & 0xffu)];
-        u32x4_t w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = __builtin_amdgcn_perm(v1, v0, sa[j]) | __builtin_amdgcn_perm(v3, v2, sb[j]);
-        return w;
-    }
+    __device__ __forceinline__ void row(const Args &a, int wrow, int fq) { BMRow::row(a.values, a.meta, a.offs, a.rowptr, a.nnz, a.N, a.K, wrow, fq); }
 };
 
 // MT tiles of 16 rows of X; D K-steps per batch (what a wave holds in registers); E the format's expansion policy
@@ -415,16 +371,24 @@ extern "C" int vlmc_linear_fwd_48_tiled(const void *X, const void *values, const
     return linear_nm_tiled("vlmc_linear_fwd_48_tiled", 48, X, values, meta, bias, dtype, M, N, K, ldx, Y, ldy, stream);
 }
 
-extern "C" int vlmc_linear_fwd_bm(const void *X, const void *values, const uint8_t *meta, const uint16_t *offs, const int64_t *rowptr, int64_t nnz,
-                                  const void *bias, int dtype, int64_t M, int64_t N, int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace,
-                                  size_t workspace_bytes, void *stream) {
-    const char *fn = "vlmc_linear_fwd_bm";
+// what both bitmap entry points ask of their arguments beyond linear_packed_check
+static int linear_bm_check(const char *fn, const void *X, const void *values, const uint8_t *meta, const uint16_t *offs, const int64_t *rowptr,
+                           int64_t nnz, int dtype, int64_t M, int64_t N, int64_t K, int64_t ldx, const void *Y, int64_t ldy) {
     const int ok = linear_packed_check(fn, X, values, meta, dtype, M, N, K, ldx, Y, ldy);
     if (ok != VLMC_OK) return ok;
     VLMC_REQUIRE(offs && rowptr, "%s: null pointer", fn);
     VLMC_REQUIRE(K <= 65536 && nnz >= 0 && nnz <= N * K, "%s: K must be at most 65536 and 0 <= nnz <= N * K", fn);
     VLMC_REQUIRE(aligned16(X) && (reinterpret_cast<uintptr_t>(values) & 3u) == 0 && (reinterpret_cast<uintptr_t>(meta) & 3u) == 0,
                  "%s: X must be 16-byte, values and meta 4-byte aligned", fn);
+    return VLMC_OK;
+}
+
+extern "C" int vlmc_linear_fwd_bm(const void *X, const void *values, const uint8_t *meta, const uint16_t *offs, const int64_t *rowptr, int64_t nnz,
+                                  const void *bias, int dtype, int64_t M, int64_t N, int64_t K, int64_t ldx, void *Y, int64_t ldy, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+    const char *fn = "vlmc_linear_fwd_bm";
+    const int ok = linear_bm_check(fn, X, values, meta, offs, rowptr, nnz, dtype, M, N, K, ldx, Y, ldy);
+    if (ok != VLMC_OK) return ok;
     if (M > VLMC_LINEARBM_MAX_ROWS) {
         const size_t dense = linear24_dense_bytes(N, K);
         VLMC_REQUIRE(workspace != nullptr && workspace_bytes >= dense + 16 && aligned16(workspace),
@@ -437,4 +401,16 @@ extern "C" int vlmc_linear_fwd_bm(const void *X, const void *values, const uint8
     const LinearBMArgs a{{static_cast<const uint16_t *>(X), static_cast<const uint16_t *>(values), meta, static_cast<const uint16_t *>(bias),
                           static_cast<uint16_t *>(Y), ldx, ldy, int(M), int(N), int(K)}, offs, rowptr, nnz};
     return linear_packed_launch<ExpandBM>(fn, a, dtype, stream);
+}
+
+extern "C" int vlmc_linear_fwd_bm_tiled_max_rows(void) { return VLMC_LINEARBM_TILED_MAX_ROWS; }
+
+// the tiled kernel at any M: no workspace, no row limit of its own
+extern "C" int vlmc_linear_fwd_bm_tiled(const void *X, const void *values, const uint8_t *meta, const uint16_t *offs, const int64_t *rowptr,
+                                        int64_t nnz, const void *bias, int dtype, int64_t M, int64_t N, int64_t K, int64_t ldx, void *Y, int64_t ldy,
+                                        void *stream) {
+    const char *fn = "vlmc_linear_fwd_bm_tiled";
+    const int ok = linear_bm_check(fn, X, values, meta, offs, rowptr, nnz, dtype, M, N, K, ldx, Y, ldy);
+    if (ok != VLMC_OK) return ok;
+    return linear_bm_tiled_launch(fn, X, values, meta, offs, rowptr, nnz, bias, dtype, M, N, K, ldx, Y, ldy, stream);
 }

@@ -93,6 +93,8 @@ SIGNATURES = {
     "vlmc_linear_fwd_bm_max_rows": (_i, []),
     "vlmc_linear_fwd_bm_workspace": (_sz, [_i64, _i64, _i64]),
     "vlmc_linear_fwd_bm": (_i, [_p, _p, _p, _p, _p, _i64, _p, _i, _i64, _i64, _i64, _i64, _p, _i64, _p, _sz, _p]),
+    "vlmc_linear_fwd_bm_tiled_max_rows": (_i, []),
+    "vlmc_linear_fwd_bm_tiled": (_i, [_p, _p, _p, _p, _p, _i64, _p, _i, _i64, _i64, _i64, _i64, _p, _i64, _p]),
     "vlmc_linear_fwd": (_i, [_p, _p, _p, _i, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p]),
     "vlmc_linear_fwd_group": (_i, [_p, _p, _i, _i, _i64, _i64, _i64, _p]),
     "vlmc_linear_fwd_rows": (_i, [_p, _p, _i, _i, _i64, _i64, _i64, _p, _i64, _p]),

@@ -781,6 +781,22 @@ def _linear_fwd_packed(tag, x, N, K, bias, unpack, packed, workspace):
     return y.reshape(*x.shape[:-1], N)
 
 
+def _linear_fwd_routed(tag, x, N, K, bias, unpack, tiled, packed, workspace, max_rows, tiled_max_rows):
+    """`_linear_fwd_packed` behind the choice every packed format offers: `tiled` sends the call to `vlmc_linear_fwd_<tag>_tiled` (the
+    packed export's arguments without the workspace) -- None: above the carried-chain kernel's `max_rows()`, up to the measured
+    `tiled_max_rows()`."""
+    rows = x.numel() // K
+    if tiled is None:
+        tiled = not unpack and max_rows() < rows <= tiled_max_rows()
+    if tiled and rows:
+        x2, M, ld = _rows(x, K, aligned=True)
+        y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+        _lib.check(getattr(_lib.load(), f"vlmc_linear_fwd_{tag}_tiled")(x2.data_ptr(), *packed, bias.data_ptr() if bias is not None else None,
+                                                                        _DT[x.dtype], M, N, K, ld, y.data_ptr(), N, _stream()))
+        return y.reshape(*x.shape[:-1], N)
+    return _linear_fwd_packed(tag, x, N, K, bias, unpack, packed, workspace)
+
+
 def _linear_fwd_nm(f, x, values, meta, bias, unpack, tiled):
     if unpack and tiled:
         raise ValueError(f"vlmc.linear_fwd_{f['tag']}: unpack=True and tiled=True name two different routes")
@@ -788,19 +804,8 @@ def _linear_fwd_nm(f, x, values, meta, bias, unpack, tiled):
     if not linear_fwd_24_supported(x, values, meta, bias):
         raise TypeError(f"vlmc.linear_fwd_{f['tag']}: fp16/bf16 x [.., K], contiguous values [N, K / 2] of the same dtype, meta [N, K / 8] uint8 "
                         "(K % 8 == 0) and a contiguous bias [N] of that dtype expected")
-    N, K = values.shape[0], 2 * values.shape[1]
-    rows = x.numel() // K
-    if tiled is None:                                       # the rule: above the carried-chain kernel's rows, up to the measured limit
-        tiled = not unpack and linear_fwd_24_max_rows() < rows <= linear_fwd_24_tiled_max_rows()
-    if tiled and rows:
-        x2, M, ld = _rows(x, K, aligned=True)
-        y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-        _lib.check(getattr(_lib.load(), f"vlmc_linear_fwd_{f['tag']}_tiled")(x2.data_ptr(), values.data_ptr(), meta.data_ptr(),
-                                                                              bias.data_ptr() if bias is not None else None, _DT[x.dtype], M, N, K,
-                                                                              ld, y.data_ptr(), N, _stream()))
-        return y.reshape(*x.shape[:-1], N)
-    return _linear_fwd_packed(f["tag"], x, values.shape[0], 2 * values.shape[1], bias, unpack, (values.data_ptr(), meta.data_ptr()),
-                              "vlmc_linear_fwd_24_workspace")
+    return _linear_fwd_routed(f["tag"], x, values.shape[0], 2 * values.shape[1], bias, unpack, tiled, (values.data_ptr(), meta.data_ptr()),
+                              "vlmc_linear_fwd_24_workspace", linear_fwd_24_max_rows, linear_fwd_24_tiled_max_rows)
 
 
 def linear_fwd_24(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, bias: torch.Tensor | None = None,
@@ -880,6 +885,13 @@ def linear_fwd_bm_max_rows() -> int:
     return int(_lib.load().vlmc_linear_fwd_bm_max_rows())
 
 
+def linear_fwd_bm_tiled_max_rows() -> int:
+    """Most rows of x that `linear_fwd_bm` gives to the TILED packed kernel (vlmc_linear_fwd_bm_tiled_max_rows): between
+    `linear_fwd_bm_max_rows()` and this the weight is expanded on its way into LDS and no scratch weight exists; above, the unpack
+    route.  0: never by default (`tiled=True` still selects it)."""
+    return int(_lib.load().vlmc_linear_fwd_bm_tiled_max_rows())
+
+
 def linear_fwd_bm_supported(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, offs: torch.Tensor, rowptr: torch.Tensor,
                             bias: torch.Tensor | None = None) -> bool:
     """Whether `linear_fwd_bm` takes this call: 16-bit x [.., K] and values [nnz + 16] of one dtype, meta [N, K / 8] uint8, offs
@@ -890,18 +902,24 @@ def linear_fwd_bm_supported(x: torch.Tensor, values: torch.Tensor, meta: torch.T
 
 
 def linear_fwd_bm(x: torch.Tensor, values: torch.Tensor, meta: torch.Tensor, offs: torch.Tensor, rowptr: torch.Tensor,
-                  bias: torch.Tensor | None = None, unpack: bool = False) -> torch.Tensor:
+                  bias: torch.Tensor | None = None, unpack: bool = False, tiled: bool | None = None) -> torch.Tensor:
     """y = x @ unpack_bm(values, meta, offs, rowptr).T + bias computed FROM the bitmap-packed weight (vlmc_linear_fwd_bm): bit for bit
     `linear_fwd(x, unpack_bm(..)[0], bias)`, any leading dims.  Up to `linear_fwd_bm_max_rows()` rows one kernel reads the packed bytes
     and expands them in registers; more rows unpack into the per-device scratch weight the n:m formats use and run the dense kernel.
     The metadata is trusted (`pack_bm` wrote it, or `formats.load_packed_bm` validated it).  `unpack`: the unpack route whatever the
-    number of rows (the cross-check of the packed kernel)."""
+    number of rows (the cross-check of the packed kernel).  `tiled`: the tiled GEMM that takes the weight operand bitmap-packed
+    (vlmc_linear_fwd_bm_tiled: any number of rows, no scratch weight, the same bits) -- None: for more than `linear_fwd_bm_max_rows()`
+    and at most `linear_fwd_bm_tiled_max_rows()` rows; True: whatever the number of rows (its cross-check; with `unpack` it raises);
+    False: never."""
+    if unpack and tiled:
+        raise ValueError("vlmc.linear_fwd_bm: unpack=True and tiled=True name two different routes")
     _need_gpu(x, values, meta, offs, rowptr, bias)
     if not linear_fwd_bm_supported(x, values, meta, offs, rowptr, bias):
         raise TypeError("vlmc.linear_fwd_bm: fp16/bf16 x [.., K], contiguous values [nnz + 16] of the same dtype, meta [N, K / 8] uint8, offs "
                         "[N, ceil(K / 32)] uint16, rowptr [N + 1] int64 (K % 8 == 0, K <= 65536) and a contiguous bias [N] of that dtype expected")
     packed = (values.data_ptr(), meta.data_ptr(), offs.data_ptr(), rowptr.data_ptr(), values.numel() - 16)
-    return _linear_fwd_packed("bm", x, meta.shape[0], 8 * meta.shape[1], bias, unpack, packed, "vlmc_linear_fwd_bm_workspace")
+    return _linear_fwd_routed("bm", x, meta.shape[0], 8 * meta.shape[1], bias, unpack, tiled, packed, "vlmc_linear_fwd_bm_workspace",
+                              linear_fwd_bm_max_rows, linear_fwd_bm_tiled_max_rows)
 
 
 def hessian_accum(H: torch.Tensor, x: torch.Tensor, alpha: float, beta: float, rows=None) -> torch.Tensor:
